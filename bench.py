@@ -31,9 +31,11 @@ edge, as SURVEY.md 8 assumes: 1.02 M edges per interaction layer at 40 poses) an
 edge count in `config`.
 
 Extra objects on the JSON line: `roofline` (dominant kernel, HIP-event timed inside the timed region) and
-`cpu_baseline` (bounded CPU sample of the same workload: the reference's own sampling() + CGModel executed under the
-third-party stand-ins of tests/golden/make_golden.py when /root/reference is present -- kind "reference-executed" --
-else the oracle = pure-torch restatement, kind "port", which is what the GPU box can run).
+`cpu_baseline` (bounded CPU sample of the same workload on the oracle = pure-torch restatement, kind "port").
+
+--dump-outputs DIR: after the timed region, the final ligand coordinates that the LAST timed step returned (what a caller of
+sample_batch receives), one float32 array per complex, DIR/complex<i>_ligand_pos.npy of shape [poses, ligand atoms, 3].
+Inputs (graphs, weights, tables, initial poses, sampling seeds) are seeded: the same arguments give the same inputs.
 """
 import argparse
 import json
@@ -57,7 +59,7 @@ from diffdock_amd.tables import default_tables  # noqa: E402
 from diffdock_amd.weights import init_state_dict  # noqa: E402
 
 INFERENCE_STEPS, SAMPLES = 20, 40
-HBM_PEAK_GBS, MFMA_F32_PEAK_TFLOPS = 8000.0, 157.3     # /opt/skills/guides/MI355X_MICROARCH.md
+HBM_PEAK_GBS, MFMA_F32_PEAK_TFLOPS = 8000.0, 157.3     # MI355X: HBM3E bandwidth, dense f32 MFMA peak
 TEMP = dict(temp_sampling=[1.170050527854316, 2.06391612594481, 7.044261621607846],       # default_inference_args.yaml
             temp_psi=[0.727287304570729, 0.9022615585677628, 0.5946212391366862],
             temp_sigma_data=[0.9299802531572672, 0.7464326999906034, 0.6943254174849822])
@@ -135,6 +137,24 @@ def copy_poses(dl):
     return copy.deepcopy(dl)
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, cap=DUMP_CAP_BYTES):
+    """{name: array [poses, ...]} -> dirname/<name>.npy in float32.  Above `cap` bytes in all, a fixed seeded sample of the poses of
+    every array is written instead, with its pose indices as <name>_pose_index.npy (float64)."""
+    os.makedirs(dirname, exist_ok=True)
+    total = sum(a.size * 4 for a in arrays.values())
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float32)
+        if total > cap:
+            keep = max(1, a.shape[0] * (cap // 2) // total)
+            idx = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            a = a[idx]
+            np.save(os.path.join(dirname, f"{name}_pose_index.npy"), idx.astype(np.float64))
+        np.save(os.path.join(dirname, f"{name}.npy"), np.ascontiguousarray(a))
+
+
 def cpu_baseline(cfg, sd, so3_t, tor_t, g, full=False):
     """Bounded CPU sample of the same workload on this host's cores: the first steps of the 20-step schedule (largest cross
     cutoffs = the same all-pairs graph as the GPU run) for a few poses, extrapolated linearly to 20 steps."""
@@ -142,63 +162,28 @@ def cpu_baseline(cfg, sd, so3_t, tor_t, g, full=False):
     torch.set_num_threads(threads)
     s = t_schedule(INFERENCE_STEPS)
     big = g["receptor"].pos.shape[0] * g["ligand"].pos.shape[0] > 50000
-    if os.path.isdir("/root/reference") and os.path.exists(os.path.join(ROOT, "tests", "golden", "make_golden.py")):
-        # the reference's own python: utils/sampling.sampling + models/cg_model.CGModel (FasterTensorProduct conv layers)
-        import copy
-        from functools import partial
-        sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
-        from make_golden import install_stubs
-        cwd = os.getcwd()
-        scratch = os.path.join(ROOT, ".scratch", "tables")
-        os.makedirs(scratch, exist_ok=True)
-        os.chdir(scratch)                  # utils/so3.py / utils/torus.py cache their tables in the working directory
-        try:
-            install_stubs()
-            from models import tensor_layers
-            tensor_layers.FasterTensorProduct.irreps_out = property(lambda self: self.out_irreps)   # reference defect, make_golden.py
-            from utils.utils import get_model
-            from utils.diffusion_utils import t_to_sigma as t_to_sigma_compl
-            from utils import sampling as ref_sampling
-            args = cfg.to_namespace()
-            t_to_sigma = partial(t_to_sigma_compl, args=args)
-            model = get_model(args, torch.device("cpu"), t_to_sigma=t_to_sigma, no_parallel=True)
-            model.load_state_dict(sd, strict=False)
-            model.eval()
-            n_s, n_steps = (1, 2) if big else (4, 5)
-            dl = make_pose_list(g, n_s, tr_sigma_max=cfg.tr_sigma_max, seed=77, initial_noise_std_proportion=0.3)
-            torch.manual_seed(0)
-            t0 = time.time()
-            ref_sampling.sampling(copy.deepcopy(dl), model, n_steps, s, s, s, torch.device("cpu"), t_to_sigma, args,
-                                  batch_size=n_s, no_final_step_noise=False, **TEMP)
-            dt = time.time() - t0
-        finally:
-            os.chdir(cwd)
-        kind = "reference-executed"
-    else:
-        from oracle.cg_model import CGModelOracle
-        from oracle.sampling import sampling as oracle_sampling
-        n_s, n_steps = (1, 2) if big else (2, 3)
-        dl = make_pose_list(g, n_s, tr_sigma_max=cfg.tr_sigma_max, seed=77, initial_noise_std_proportion=0.3)
-        model = CGModelOracle(cfg, sd, so3_t, tor_t)
-        R = int(dl[0]["ligand"].edge_mask.sum())
-        gen = torch.Generator().manual_seed(0)
-        noise = (torch.randn(INFERENCE_STEPS, n_s, 3, generator=gen), torch.randn(INFERENCE_STEPS, n_s, 3, generator=gen),
-                 torch.randn(INFERENCE_STEPS, n_s * R, generator=gen))
-        # the per-edge einsums of the restated tensor product stop scaling after a few dozen threads: time the sample at 16 threads
-        # and at every core (<= 64), report the faster one as the baseline and both in `thread_scaling`
-        scaling = {}
-        for th in ([threads] if big or threads <= 16 else [16, threads]):
-            torch.set_num_threads(th)
-            t0 = time.time()
-            oracle_sampling(copy_poses(dl), model, n_steps, cfg, noise, schedules=(s, s, s), batch_size=n_s, **TEMP)
-            scaling[th] = time.time() - t0
-        threads = min(scaling, key=scaling.get)
-        dt = scaling[threads]
-        thread_scaling = {str(th): round(n_s / (t / n_steps * INFERENCE_STEPS), 5) for th, t in scaling.items()}
-        kind = "port"
+    from oracle.cg_model import CGModelOracle
+    from oracle.sampling import sampling as oracle_sampling
+    n_s, n_steps = (1, 2) if big else (2, 3)
+    dl = make_pose_list(g, n_s, tr_sigma_max=cfg.tr_sigma_max, seed=77, initial_noise_std_proportion=0.3)
+    model = CGModelOracle(cfg, sd, so3_t, tor_t)
+    R = int(dl[0]["ligand"].edge_mask.sum())
+    gen = torch.Generator().manual_seed(0)
+    noise = (torch.randn(INFERENCE_STEPS, n_s, 3, generator=gen), torch.randn(INFERENCE_STEPS, n_s, 3, generator=gen),
+             torch.randn(INFERENCE_STEPS, n_s * R, generator=gen))
+    # the per-edge einsums of the restated tensor product stop scaling after a few dozen threads: time the sample at 16 threads
+    # and at every core (<= 64), report the faster one as the baseline and both in `thread_scaling`
+    scaling = {}
+    for th in ([threads] if big or threads <= 16 else [16, threads]):
+        torch.set_num_threads(th)
+        t0 = time.time()
+        oracle_sampling(copy_poses(dl), model, n_steps, cfg, noise, schedules=(s, s, s), batch_size=n_s, **TEMP)
+        scaling[th] = time.time() - t0
+    threads = min(scaling, key=scaling.get)
+    dt = scaling[threads]
+    thread_scaling = {str(th): round(n_s / (t / n_steps * INFERENCE_STEPS), 5) for th, t in scaling.items()}
     poses_per_s = n_s / (dt / n_steps * INFERENCE_STEPS)
-    return {"value": poses_per_s, "unit": "poses/s", "cores": threads, "kind": kind,
-            **({"thread_scaling_poses_per_s": thread_scaling} if kind == "port" else {}),
+    return {"value": poses_per_s, "unit": "poses/s", "cores": threads, "kind": "port", "thread_scaling_poses_per_s": thread_scaling,
             "sample": f"{n_s} poses x the first {n_steps} of {INFERENCE_STEPS} steps of the "
                       f"{g['receptor'].pos.shape[0]}-residue / {g['ligand'].pos.shape[0]}-atom complex, same weights, extrapolated "
                       f"linearly to {INFERENCE_STEPS} steps; torch {torch.__version__}, {threads} threads, {dt:.1f} s wall"}
@@ -244,7 +229,11 @@ def main():
     ap.add_argument("--no-verify-shards", dest="verify_shards", action="store_false")
     ap.add_argument("--all-atoms", action="store_true",
                     help="secondary workload: the all-atom score model (models/aa_model.py), ~7.5 receptor atoms per residue")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the final ligand coordinates of the last timed step (one float32 .npy per complex, rank 0) to DIR")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     rank = int(os.environ.get("RANK", 0))
     local_rank = int(os.environ.get("LOCAL_RANK", 0))
     world = int(os.environ.get("WORLD_SIZE", 1))
@@ -348,7 +337,8 @@ def main():
             print(f"[trace rank {rank}] {time.perf_counter() - t_origin:10.4f} s  {what}", file=sys.stderr, flush=True)
 
     def one_step(seed, jobs_=None):
-        last = None
+        """one 20-step sampling pass of every complex; returns the rank's final ligand coordinates of each complex"""
+        outs = []
         for j in (jobs if jobs_ is None else jobs_):
             trace(f"seed {seed}: enqueue sample_job ({len(j['ids'])} poses)")
             pos = sample_job(j, seed)
@@ -373,8 +363,8 @@ def main():
                 else:
                     dist.all_gather(j["gathered"], buf)
                 trace("  all_gather returned")
-            last = pos
-        return last
+            outs.append(pos)
+        return outs
 
     def timed(steps, jobs_=None):
         """K steps bracketed by barrier + synchronize on both sides; MAX over the ranks."""
@@ -384,7 +374,7 @@ def main():
         t0 = time.perf_counter()
         last = None
         for k in range(steps):
-            last = one_step(100 + k, jobs_)
+            last = one_step(100 + k, jobs_)       # (only the last step's outputs are kept: no copies inside the region)
         if world > 1:
             dist.barrier()
             trace("barrier behind the timed steps returned")
@@ -398,7 +388,16 @@ def main():
 
     for w in range(args.warmup):
         one_step(w)
-    dt, pos = timed(args.steps)           # the timed region: per-kernel timers off
+    dt, outs = timed(args.steps)          # the timed region: per-kernel timers off
+    pos = outs[-1]
+    if args.dump_outputs and rank == 0:
+        # what the last timed step returned, copied off the device before anything else runs (later passes reuse the gather buffers)
+        dumps = {}
+        for i, (j, o) in enumerate(zip(jobs, outs)):
+            if world > 1:     # the caller of the sharded path receives the gathered poses of all ranks
+                o = torch.cat([j["gathered"][r][:(shard_bounds(S, r, world)[1] - shard_bounds(S, r, world)[0]) * j["n_lig"]]
+                               for r in range(world)]) if strong else torch.cat(j["gathered"])
+            dumps[f"complex{i}_ligand_pos"] = o.detach().cpu().reshape(-1, j["n_lig"], 3).numpy()
     weak_extra = None
     if strong:
         # extra key: the weak-scaling figure (every rank its own S poses of each complex), one warm-up + one timed step
@@ -506,6 +505,8 @@ def main():
         mdl.set_kernel_timing(False)
     timed_steps = 1                       # steps behind `timings`
     assert os.environ.get("DDMI_BENCH_NOCHECK") or torch.isfinite(pos).all()   # NOCHECK: timing-only ablation builds
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dumps)
 
     if rank == 0:
         # edges actually processed by the last forward of the run, per complex

@@ -74,3 +74,24 @@ def test_traffic_record_of_another_kernel_source_is_not_replayed(tmp_path):
 def test_roofline_constants_match_the_microarchitecture_guide():
     b = load_bench()
     assert b.MFMA_F32_PEAK_TFLOPS == 157.3 and b.HBM_PEAK_GBS == 8000.0
+
+
+def test_dump_outputs_writes_float32_arrays_and_keeps_under_the_cap(tmp_path):
+    """bench.py --dump-outputs: one float32 .npy per array as given; above the cap a fixed seeded sample of the poses, with its indices."""
+    import numpy as np
+    b = load_bench()
+    a = np.arange(40 * 30 * 3, dtype=np.float32).reshape(40, 30, 3)
+    b.dump_outputs(str(tmp_path / "full"), {"complex0_ligand_pos": a})
+    got = np.load(tmp_path / "full" / "complex0_ligand_pos.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, a)
+    assert sorted(os.listdir(tmp_path / "full")) == ["complex0_ligand_pos.npy"]
+    cap = a.nbytes // 2
+    for d in ("s1", "s2"):
+        b.dump_outputs(str(tmp_path / d), {"complex0_ligand_pos": a}, cap=cap)
+    files = sorted(os.listdir(tmp_path / "s1"))
+    assert files == ["complex0_ligand_pos.npy", "complex0_ligand_pos_pose_index.npy"]
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in files) <= cap
+    idx = np.load(tmp_path / "s1" / "complex0_ligand_pos_pose_index.npy")
+    sample = np.load(tmp_path / "s1" / "complex0_ligand_pos.npy")
+    assert idx.dtype == np.float64 and 0 < len(idx) < 40 and np.array_equal(sample, a[idx.astype(int)])
+    assert np.array_equal(idx, np.load(tmp_path / "s2" / "complex0_ligand_pos_pose_index.npy"))   # the sample is fixed

@@ -1,5 +1,7 @@
 """diffdock_amd.io: PDB / SDF readers and graph construction on the reference's example complex."""
+import gzip
 import os
+import shutil
 import subprocess
 
 import numpy as np
@@ -15,7 +17,7 @@ from util import load_fixture, tables
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EMU = os.path.join(ROOT, "tests", "hipemu", "libddmi_emu.so")
-REF_DATA = "/root/reference/data/1a0q"
+REF_DATA = os.path.join(ROOT, "tests", "golden", "1a0q")      # the reference's example complex (data/1a0q), stored gzip-compressed
 
 
 def test_fixture_has_the_documented_sizes():
@@ -30,12 +32,20 @@ def test_fixture_has_the_documented_sizes():
     assert int(d["edge_mask"].sum()) == d["mask_rotate"].shape[0]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DATA), reason="the reference's data directory exists only in the build container")
-def test_io_reproduces_the_reference_executed_fixture_bit_for_bit():
+def ref_data(tmp_path):
+    """the stored data/1a0q files, decompressed into tmp_path (the readers take plain file paths)"""
+    for name in ("1a0q_protein_processed.pdb", "1a0q_ligand.sdf"):
+        with gzip.open(os.path.join(REF_DATA, name + ".gz"), "rb") as src, open(tmp_path / name, "wb") as dst:
+            shutil.copyfileobj(src, dst)
+    return str(tmp_path)
+
+
+def test_io_reproduces_the_reference_executed_fixture_bit_for_bit(tmp_path):
     """diffdock_amd.io against the fixture whose receptor graph / features / positions and rotatable-bond masks were produced
     by EXECUTING the reference (datasets/process_mols.py new_extract_receptor_structure, utils/torsion.py
     get_transformation_mask, the centring of datasets/pdbbind.py; tests/golden/make_1a0q.py)."""
-    g = complex_graph(f"{REF_DATA}/1a0q_protein_processed.pdb", f"{REF_DATA}/1a0q_ligand.sdf", lm_dim=0)
+    data = ref_data(tmp_path)
+    g = complex_graph(f"{data}/1a0q_protein_processed.pdb", f"{data}/1a0q_ligand.sdf", lm_dim=0)
     d = load_fixture("1a0q_graph")
     assert "process_mols.py new_extract_receptor_structure executed" in d["provenance"]
     assert torch.equal(g["receptor"].pos, d["rec_pos"]) and torch.equal(g["receptor", "receptor"].edge_index, d["rec_edge_index"])
@@ -43,7 +53,7 @@ def test_io_reproduces_the_reference_executed_fixture_bit_for_bit():
     assert torch.equal(g["ligand"].pos, d["lig_pos"]) and torch.equal(g["ligand", "ligand"].edge_index, d["bond_index"])
     assert torch.equal(g["ligand"].edge_mask, d["edge_mask"])
     assert np.array_equal(np.asarray(g["ligand"].mask_rotate[0]), d["mask_rotate"].numpy())
-    xyz, z, bonds = read_sdf(f"{REF_DATA}/1a0q_ligand.sdf", remove_hs=False)
+    xyz, z, bonds = read_sdf(f"{data}/1a0q_ligand.sdf", remove_hs=False)
     assert len(z) == 45 and int((z == 1).sum()) == 22 and len(bonds) == 45
 
 
