@@ -294,17 +294,28 @@ __device__ __forceinline__ void fc_store_rows(const float* __restrict__ stg, int
 // Uniform-base requests (buffer resource in SGPRs + 32-bit lane offset + SGPR offset): no per-request 64-bit address
 // arithmetic in the vector ALU and no address registers -- the dense main loop issues one such request per MFMA shadow.
 #ifdef DDMI_HIPEMU
-struct FcBuf { const char* p; };
-__device__ __forceinline__ FcBuf fc_buf(const void* p, unsigned) { return FcBuf{reinterpret_cast<const char*>(p)}; }
+// The emulator keeps the range of the resource: on the GPU every dword at or past `bytes` reads as 0, which would hide a
+// range that is too small (weights or hidden rows silently zeroed) -- here such a request aborts with its offset instead.
+struct FcBuf { const char* p; unsigned bytes; };
+__device__ __forceinline__ FcBuf fc_buf(const void* p, unsigned bytes) { return FcBuf{reinterpret_cast<const char*>(p), bytes}; }
+__device__ __forceinline__ const float* fc_buf_at(const FcBuf& b, unsigned voff, unsigned soff, unsigned n) {
+  const unsigned long long off = (unsigned long long)voff + soff;
+  if (off + 4ull * n > b.bytes) {
+    fprintf(stderr, "fc_buf: %u-dword load at byte %llu (voff %u + soff %u) past the buffer range of %u bytes\n", n, off, voff, soff, b.bytes);
+    abort();
+  }
+  return reinterpret_cast<const float*>(b.p + off);
+}
 __device__ __forceinline__ float4 fc_buf_ld4(const FcBuf& b, unsigned voff, unsigned soff) {
-  return *reinterpret_cast<const float4*>(b.p + voff + soff);
+  const float* q = fc_buf_at(b, voff, soff, 4);
+  return make_float4(q[0], q[1], q[2], q[3]);
 }
 __device__ __forceinline__ float3 fc_buf_ld3(const FcBuf& b, unsigned voff, unsigned soff) {
-  const float* q = reinterpret_cast<const float*>(b.p + voff + soff);
+  const float* q = fc_buf_at(b, voff, soff, 3);
   return make_float3(q[0], q[1], q[2]);
 }
 __device__ __forceinline__ f32x4 fc_buf_ld4v(const FcBuf& b, unsigned voff, unsigned soff) {
-  const float* q = reinterpret_cast<const float*>(b.p + voff + soff);
+  const float* q = fc_buf_at(b, voff, soff, 4);
   return f32x4{q[0], q[1], q[2], q[3]};
 }
 #else

@@ -4,6 +4,7 @@ moves a batch to the model's device."""
 import copy
 
 import numpy as np
+import pytest
 import torch
 
 from diffdock_amd.config import TINY
@@ -162,3 +163,362 @@ def config0_case(make, place, cfg, tol_pos=2e-3, steps=4):
     r = rmsd(pos, ref_pos)
     assert float(r.max()) < tol_pos, r
     return r
+
+
+# ---- edge shapes and forced kernel routes (tests/test_emu_parity.py on the emulator, tests/test_gpu_edges.py on the MI355X) ----
+# `setenv(name, value)` sets a DDMI_* route variable (monkeypatch.setenv): diffdock_amd/lib.py reads it when a
+# model handle is created, so every handle below is made after its variables are set.  The reference is the float64 oracle.
+F64 = torch.float64
+
+def _synth(cfg, n_res, n_lig, B, seed, pose_seed, t, noise=0.3):
+    from diffdock_amd.synth import make_pose_list as mpl
+    g = make_complex(seed=seed, n_res=n_res, n_lig=n_lig, lm_dim=0)
+    b = HeteroBatch.from_data_list(mpl(g, B, tr_sigma_max=cfg.tr_sigma_max, seed=pose_seed, initial_noise_std_proportion=noise))
+    set_time(b, t, t, t, B)
+    return b
+
+
+def _ddl(**kw):
+    from diffdock_amd.config import DDL_SYNTH
+    base = dict(lm_embedding_type=None, dynamic_max_cross=False, cross_max_distance=80.0, tr_sigma_max=5.0)
+    base.update(kw)
+    return DDL_SYNTH.replace(**base)
+
+
+def no_cross_edges_and_ragged_batch_case(make, place):
+    """Edge cases the reference handles (with e3nn tensor products): a ligand out of cross-graph range (empty cross groups)
+    and a batch of two DIFFERENT complexes (ragged sizes); then no cross edge in the whole batch."""
+    cfg = TINY.replace(sh_lmax=2)
+    sd = init_state_dict(cfg, seed=5)
+    g1, g2 = make_complex(seed=11, n_res=24, n_lig=9), make_complex(seed=12, n_res=31, n_lig=13)
+    g1["ligand"].pos = g1["ligand"].pos + torch.tensor([[500.0, 0.0, 0.0]])   # far away: no cross edges for graph 0
+    for all_far in (False, True):
+        if all_far:
+            g2["ligand"].pos = g2["ligand"].pos + torch.tensor([[0.0, 700.0, 0.0]])    # now NO cross edges at all
+        batch = HeteroBatch.from_data_list([g1, g2])
+        set_time(batch, 0.4, 0.4, 0.4, 2)
+        # (float32 oracle: the ligand 500 A away carries float32 coordinates, and on this input the float32 oracle itself is
+        # 1.4e-4 of max|tr| away from the float64 one -- the input's rounding, shared by every float32 form)
+        ref = oracle_model(cfg, sd)(batch, return_intermediates=True)
+        m = make(cfg, sd)
+        out = m(place(batch))
+        n_cross = int(m.debug_buffer("offs_l")[-1])
+        assert n_cross == ref[4]["edge_counts"][1] and (n_cross == 0) == all_far
+        assert_scores_close(out[:3], ref[:3], what=f"no cross edges (all={all_far})")
+
+
+def rigid_ligand_case(make, place, no_torsion):
+    """cg_model.py:404: a ligand without rotatable bonds, or `no_torsion`, returns (tr, rot, empty(0), None); the device loop
+    then runs the rigid-body update only (modify_conformer_batch with zero torsions)."""
+    cfg = TINY.replace(no_torsion=no_torsion)
+    sd = init_state_dict(cfg, seed=5)
+    g = make_complex(seed=11, n_res=20, n_lig=8)
+    if not no_torsion:
+        g["ligand"].edge_mask = torch.zeros_like(g["ligand"].edge_mask)
+        g["ligand"].mask_rotate = [g["ligand"].mask_rotate[0][:0]]
+    dl = make_pose_list(g, 2, tr_sigma_max=cfg.tr_sigma_max, seed=3, no_torsion=no_torsion)
+    b = HeteroBatch.from_data_list(dl)
+    set_time(b, 0.5, 0.5, 0.5, 2)
+    ref = oracle_model(cfg, sd, dtype=F64)(b)
+    m = make(cfg, sd)
+    tr, rot, tor, none = m(place(b))
+    assert none is None and ref[3] is None and tor.shape == (0,) and ref[2].shape == (0,)
+    assert_scores_close((tr, rot), ref[:2], what="rigid ligand")
+    sched = get_t_schedule(3)
+    start = b["ligand"].pos.cpu().clone()
+    pos = m.sample_batch(place(b), 3, (sched, sched, sched), seed=1, no_final_step_noise=True).cpu()
+    assert pos.shape == start.shape and torch.isfinite(pos).all()
+    assert (pos - start).abs().max() > 1e-3                                 # the poses did move
+    # rigid motion only: the intramolecular distances of every pose are those of the start conformer
+    for k in range(2):
+        a0, a1 = start.reshape(2, -1, 3)[k], pos.reshape(2, -1, 3)[k]
+        assert (torch.cdist(a0, a0) - torch.cdist(a1, a1)).abs().max() < 1e-3
+
+
+def degenerate_sizes_case(make, place, n_res, n_lig, B):
+    """A batch of one pose, a 3-residue receptor (fewer neighbours than the 24-nearest graph asks for), a 2-atom ligand:
+    forward against the oracle, and the device loop stays finite."""
+    cfg = TINY
+    sd = init_state_dict(cfg, seed=5)
+    g = make_complex(seed=11, n_res=n_res, n_lig=n_lig)
+    b = HeteroBatch.from_data_list(make_pose_list(g, B, tr_sigma_max=cfg.tr_sigma_max, seed=3))
+    set_time(b, 0.5, 0.5, 0.5, B)
+    ref = oracle_model(cfg, sd, dtype=F64)(b)
+    m = make(cfg, sd)
+    out = m(place(b))
+    for o, r, name in zip(out[:3], ref[:3], ("tr", "rot", "tor")):
+        assert o.shape == r.shape, name
+        if r.numel():
+            assert_scores_close((o,), (r,), names=(name,), what=f"{n_res}/{n_lig}/{B}")
+    sched = get_t_schedule(3)
+    pos = m.sample_batch(place(b), 3, (sched, sched, sched), seed=1, no_final_step_noise=True)
+    assert pos.shape == b["ligand"].pos.shape and torch.isfinite(pos).all()
+
+
+def fused_conv_full_width_case(make, place, setenv, lmax, edge_product="f32"):
+    """DDL-synth channel widths (ns=48, nv=10) on a small complex: the statically-shaped main loop of k_conv_fused
+    (chain shapes (12,3,3,3)/(3,3,3,3)/(12,-,-,-) and the packed 12|3x3 granule of the second layer), the generic variant at
+    sh_lmax=2, receptor residues with more than 32 ligand neighbours (two virtual nodes per residue), against the oracle, with
+    the dense-row and the sparse-row loop; at sh_lmax=1 also the merged first-layer granule against the separate granules."""
+    cfg = _ddl(num_conv_layers=2, sh_lmax=lmax, edge_product=edge_product)
+    sd = init_state_dict(cfg, seed=3)
+    b = _synth(cfg, 12, 40, 2, seed=1, pose_seed=5, t=0.6)
+    ref = oracle_model(cfg, sd, dtype=F64)(b)[:3]
+    outs = {}
+    for dense in ("1", "0"):          # dense-row and sparse-row loops (lmax 2: the generic, compiler-scheduled variant both times)
+        setenv("DDMI_FUSED_DENSE", dense)
+        m = make(cfg, sd)
+        m.set_kernel_timing(True)
+        outs[dense] = [o.cpu() for o in m(place(b))[:3]]
+        assert "k_conv_fused" in m.kernel_timings()
+        assert int(m.debug_buffer("vn_off_cross")[-1]) == 2 * b["receptor"].pos.shape[0]   # 40 neighbours -> 2 virtual nodes
+        assert_scores_close(outs[dense], ref, what=f"dense={dense}")
+    for a_, b_ in zip(outs["1"], outs["0"]):
+        assert rel_err(a_, b_) < 1e-5
+    if lmax == 1:   # the merged first-layer granule (three scalar channel tiles in one) against the separate granules
+        setenv("DDMI_FUSED_TRI", "0")
+        sep = [o.cpu() for o in make(cfg, sd)(place(b))[:3]]
+        assert_scores_close(sep, ref, what="tri=0")
+        for a_, b_ in zip(outs["0"], sep):
+            assert rel_err(a_, b_) < 1e-5
+
+
+def packing_dropped_case(make, place, setenv, ns, listing=None):
+    """ns = 16 / 32 with nv = 10: the 4- / 8-step scalar chains are outside the static shape set, so every layer with a scalar
+    input path runs the predicated kernel variant, which walks classic 4-slot granules only.  Such a layer must not contain a
+    packed granule (round-3 defect: its slots 4..6 were dropped, 1 % error in the 1e block); packing on / off must agree.
+    `listing()` (optional) returns the granule listing printed while a handle was created under DDMI_DEBUG_GRAN."""
+    cfg = _ddl(ns=ns, nv=10, num_conv_layers=4)
+    sd = init_state_dict(cfg, seed=3)
+    b = _synth(cfg, 10, 12, 2, seed=1, pose_seed=5, t=0.6)
+    ref = oracle_model(cfg, sd, dtype=F64)(b)[:3]
+    outs = {}
+    if listing is not None:
+        setenv("DDMI_DEBUG_GRAN", "1")
+        listing()
+    for pack in ("1", "0"):
+        setenv("DDMI_FUSED_PACK", pack)
+        m = make(cfg, sd)
+        if listing is not None:
+            lines = [ln for ln in listing().splitlines() if ln.startswith("ddmi granules")]
+            assert lines
+            for line in lines:
+                if "[shape 0 " in line:
+                    assert not any(f"[shape {s} " in line for s in (4, 5, 6, 7)), line
+        outs[pack] = [o.cpu() for o in m(place(b))[:3]]
+        assert_scores_close(outs[pack], ref, what=f"pack={pack}")
+        for o, r in zip(outs[pack], ref):
+            assert rel_err(o, r) < 1e-5
+    for a_, b_ in zip(outs["1"], outs["0"]):
+        assert rel_err(a_, b_) < 1e-5
+
+
+def shared_node_contraction_case(make, place, setenv, edge_product="f32"):
+    """Shared-node tiles of k_conv_fused (MODE 4: the x tile holds the distinct gather nodes of the 16 virtual nodes, classic
+    granules contract them on the 4x4x1 MFMA, packed granules read their rows through the slot map), forced onto EVERY edge
+    group (DDMI_FUSED_SHARED=2 with dense rows): tiles with 16 distinct nodes (four passes), tiles that mix nodes with one and
+    several virtual nodes, the bias row, against the oracle and against the per-virtual-node form."""
+    cfg = _ddl(num_conv_layers=4, edge_product=edge_product)
+    sd = init_state_dict(cfg, seed=3)
+    b = _synth(cfg, 75, 7, 2, seed=2, pose_seed=5, t=0.6)     # 75 receptor neighbours per ligand atom: 32 + 32 + 11 edges
+    ref = oracle_model(cfg, sd, dtype=F64)(b)[:3]
+    setenv("DDMI_FUSED_DENSE", "2")
+    outs = {}
+    for shared in ("2", "1", "0"):
+        setenv("DDMI_FUSED_SHARED", shared)
+        m = make(cfg, sd)
+        outs[shared] = [o.cpu() for o in m(place(b))[:3]]
+        assert int(m.debug_buffer("vn_off_rl")[-1]) == 3 * b["ligand"].pos.shape[0]
+        assert_scores_close(outs[shared], ref, what=f"shared={shared}")
+    for k in ("2", "1"):
+        for a_, b_ in zip(outs[k], outs["0"]):
+            assert rel_err(a_, b_) < 1e-5
+
+
+def in_tile_pre_reduction_case(make, place, setenv, edge_product="f32"):
+    """lig<-rec group: the 16 residues of a tile send to the same <= 32 ligand atoms, so a tile sums its message rows per target in
+    LDS (per wave, then the eight partial sums in wave order) and ONE row per (tile, target) leaves it; k_reduce_bn reads only the
+    rows flagged live (tensor_layers.py:144,220-221: the scatter-mean itself is unchanged -- counts are the true edge counts).
+    3 poses x 12 residues x 20 atoms: tiles 0 and 1 straddle two poses (targets span 40 rows: one row per edge as before), tile 2
+    is pre-reduced.  Against the oracle and against the per-edge route (DDMI_FUSED_PRERED=0)."""
+    cfg = _ddl(num_conv_layers=4, edge_product=edge_product)
+    sd = init_state_dict(cfg, seed=3)
+    b = _synth(cfg, 12, 20, 3, seed=1, pose_seed=5, t=0.6)
+    ref = oracle_model(cfg, sd, dtype=F64)(b)[:3]
+    outs = {}
+    for pre in ("1", "0"):
+        setenv("DDMI_FUSED_PRERED", pre)
+        m = make(cfg, sd)
+        outs[pre] = [o.cpu() for o in m(place(b))[:3]]
+        if pre == "1":
+            hdr = m.debug_buffer("prered_tile_hdr")
+            assert hdr[:3, 0].tolist() == [0, 0, 1] and hdr[2, 1:3].tolist() == [40, 20]   # (mode, first target row, span)
+            assert (hdr[2, 4:24] >= 0).all() and (hdr[2, 24:36] == -1).all()            # one message row per target of the tile
+        assert_scores_close(outs[pre], ref, what=f"prered={pre}")
+    for a_, b_ in zip(outs["1"], outs["0"]):
+        assert rel_err(a_, b_) < 1e-5
+
+
+def readout_tensor_product_forms_case(make, place, setenv, name):
+    """final_conv / tor_bond_conv in the direct (per-edge-weight) form: the wave-per-item, thread-per-item and
+    workgroup-per-edge kernels (k_readout.hip; picked by launch size in production, forced here) against the reference fixture."""
+    from util import fixture_case
+    fx, cfg, data_list = fixture_case(name)
+    batch = HeteroBatch.from_data_list(data_list)
+    set_time(batch, fx["t"], fx["t"], fx["t"], batch.num_graphs)
+    ref = fx["forward"]
+    for form in ("edge", "thread", "wave"):
+        setenv("DDMI_TP_APPLY", form)
+        tr, rot, tor, _ = make(cfg, fx["state_dict"])(place(batch))
+        assert_scores_close((tr, rot, tor), (ref["tr"], ref["rot"], ref["tor"]), what=form)
+
+
+def many_receptor_neighbours_case(make, place):
+    """Ligand-gather groups through the fused kernel with several virtual nodes per ligand atom (70 receptor neighbours ->
+    32 + 32 + 6 edges: the node term is repeated per virtual node, the last one is a sparse tile) at a width the MFMA first
+    layer and the dense-row loop accept (ns = 16), against the oracle."""
+    cfg = TINY.replace(ns=16, nv=4, sh_lmax=1, num_conv_layers=3, dynamic_max_cross=False, cross_max_distance=200.0,
+                       lm_embedding_type=None)
+    sd = init_state_dict(cfg, seed=9)
+    g = make_complex(seed=21, n_res=70, n_lig=5, lm_dim=0)
+    b = HeteroBatch.from_data_list(make_pose_list(g, 2, tr_sigma_max=cfg.tr_sigma_max, seed=4))
+    set_time(b, 0.5, 0.5, 0.5, 2)
+    ref = oracle_model(cfg, sd, dtype=F64)(b)[:3]
+    m = make(cfg, sd)
+    m.set_kernel_timing(True)
+    out = m(place(b))[:3]
+    assert "k_conv_fused" in m.kernel_timings()
+    assert int(m.debug_buffer("vn_off_rl")[-1]) == 3 * b["ligand"].pos.shape[0]     # ceil(70 / 32) virtual nodes per ligand atom
+    assert int(m.debug_buffer("vn_off_cross")[-1]) == b["receptor"].pos.shape[0]    # 5 ligand neighbours: one sparse tile each
+    assert_scores_close(out, ref, what="many receptor neighbours")
+
+
+def fused_node_update_case(make, place, modes=(1, 2), edge_product="f32"):
+    """ddmi_exec_options.node_update = 1: k_node_update (a layer's node rows AND the next layer's per-node first-Linear terms P / Q in
+    one kernel, the per-graph sigma terms of every layer from one batched launch) against k_reduce_bn + k_gemm_nt_batch launches:
+    the node tables are the same sums in the same order -- layer 1's table, which no fused P / Q has touched yet, is bit-identical --
+    and the scores agree at rounding level (P / Q take a 48-term fp32 sum in another order) and with the oracle.  With the per-step
+    crop (its own reduce-group list), sidechain rows (the last layer reduces every row), a ragged batch of two complexes.
+    node_update 2 / 3 force the workgroup shapes (sixteen nodes per workgroup / four waves per node)."""
+    cfg = _ddl(num_conv_layers=3, tr_sigma_min=0.1, tr_sigma_max=0.5, sidechain_pred=True, edge_product=edge_product)
+    sd = init_state_dict(cfg, seed=3)
+    g1 = make_complex(seed=4, n_res=19, n_lig=10, lm_dim=0)
+    g2 = make_complex(seed=5, n_res=13, n_lig=7, lm_dim=0)
+    dl = make_pose_list(g1, 2, tr_sigma_max=5.0, seed=6, initial_noise_std_proportion=0.3) + make_pose_list(g2, 1, tr_sigma_max=5.0, seed=7, initial_noise_std_proportion=0.3)
+    sched = get_t_schedule(1)
+    res = {}
+    for mode in (0,) + tuple(modes):
+        m = make(cfg.replace(exec_options=(("node_update", mode),) if mode else ()), sd)
+        b = HeteroBatch.from_data_list(dl)
+        set_time(b, 0.6, 0.6, 0.6, b.num_graphs)
+        m.set_kernel_timing(True)
+        out = [o.cpu().clone() for o in m(place(b))]
+        timers = m.kernel_timings()
+        m.set_kernel_timing(False)
+        x1 = torch.from_numpy(m.debug_buffer("x1").copy())
+        cropped, traj = None, None
+        if mode in (0, 1):
+            m.set_crop_cutoff(6.0)
+            cropped = [o.cpu().clone() for o in m(place(b))]
+            m.set_crop_cutoff(None)
+            traj = m.sample_batch(place(HeteroBatch.from_data_list(dl[:2])), 1, (sched, sched, sched), seed=11, sample_ids=[0, 1],
+                                  no_final_step_noise=True).cpu().clone()
+        res[mode] = (out, x1, cropped, traj, timers)
+    # launches of the first-Linear GEMMs per forward: per layer and group before, the first layer's batch + the sigma batch now
+    assert res[0][4]["conv_fc1_gemms"][1] > 2
+    b = HeteroBatch.from_data_list(dl)
+    set_time(b, 0.6, 0.6, 0.6, b.num_graphs)
+    ref = oracle_model(cfg, sd, dtype=F64)(b)
+    for mode in modes:
+        assert res[mode][4]["conv_fc1_gemms"][1] == 2
+        if mode != 1 and 1 in res:   # same sums, same MFMA chains whichever workgroup shape
+            assert torch.equal(res[mode][0][0], res[1][0][0]) and torch.equal(res[mode][0][2], res[1][0][2]), mode
+        assert torch.equal(res[mode][1], res[0][1])          # first interaction layer's node table
+        for a_, b_ in zip(res[mode][0], res[0][0]):
+            assert rel_err(a_, b_) < 1e-5
+        if res[mode][2] is not None:
+            for a_, b_ in zip(res[mode][2], res[0][2]):
+                assert a_.shape == b_.shape and rel_err(a_, b_) < 1e-5
+            assert (res[mode][3] - res[0][3]).abs().max() < 1e-4
+        assert_scores_close(res[mode][0][:3], ref[:3], what=f"node_update={mode}")
+    return res
+
+
+def all_atom_ragged_batch_case(make, place):
+    """AAModel on a batch of two DIFFERENT complexes (residue / atom / ligand counts differ), first with one ligand out of
+    reach of every receptor atom, then with the ligand<->atom group completely empty (the reference's FasterTensorProduct
+    cannot run that; sh_lmax = 2 can), against the oracle."""
+    cfg = TINY.replace(all_atoms=True, sh_lmax=2, num_conv_layers=3, dynamic_max_cross=False, cross_max_distance=60.0)
+    sd = init_state_dict(cfg, seed=2)
+    g1 = make_complex(seed=31, n_res=14, n_lig=7, all_atoms=True, atoms_per_res=(2, 5))
+    g2 = make_complex(seed=32, n_res=19, n_lig=11, all_atoms=True, atoms_per_res=(2, 5))
+    d1 = make_pose_list(g1, 1, tr_sigma_max=5.0, seed=1, initial_noise_std_proportion=0.05)[0]
+    d2 = make_pose_list(g2, 1, tr_sigma_max=5.0, seed=2, initial_noise_std_proportion=0.05)[0]
+    d2["ligand"].pos = d2["ligand"].pos + torch.tensor([30.0, 0.0, 0.0])
+    m = make(cfg, sd)
+    for empty in (False, True):
+        if empty:
+            d1["ligand"].pos = d1["ligand"].pos + torch.tensor([0.0, 40.0, 0.0])
+        batch = HeteroBatch.from_data_list([d1, d2])
+        set_time(batch, 0.5, 0.5, 0.5, 2)
+        ref = oracle_model(cfg, sd, dtype=F64)(batch, return_intermediates=True)
+        assert (ref[4]["edge_counts"][2] == 0) == empty
+        out = m(place(batch))
+        assert int(m.debug_buffer("offs_la_l")[-1]) == ref[4]["edge_counts"][2]
+        assert_scores_close(out[:3], ref[:3], what=f"all-atom ragged (empty={empty})")
+
+
+def crop_with_embedding_layers_case(make, place):
+    """crop_beyond + receptor embedding layers: the reference re-embeds the CROPPED receptor each step."""
+    from oracle.sampling import sampling as oracle_sampling
+    from util import fixture_case
+    fx, cfg, data_list = fixture_case("tiny_l1_1group_emb")
+    cfg = cfg.replace(crop_beyond=9.0)
+    B, R = len(data_list), int(data_list[0]["ligand"].edge_mask.sum())
+    g = torch.Generator().manual_seed(1)
+    steps = 3
+    noise = (torch.randn(steps, B, 3, generator=g), torch.randn(steps, B, 3, generator=g), torch.randn(steps, B * R, generator=g))
+    ref = oracle_sampling([d.clone() for d in data_list], oracle_model(cfg, fx["state_dict"]), steps, cfg, noise,
+                          batch_size=B, no_final_step_noise=True)
+    ref = torch.stack([d["ligand"].pos for d in ref])
+    m = make(cfg, fx["state_dict"])
+    sched = get_t_schedule(steps)
+    pos = m.sample_batch(place(HeteroBatch.from_data_list(data_list)), steps, (sched, sched, sched), noise=noise,
+                         no_final_step_noise=True, crop_beyond=cfg.crop_beyond).cpu()
+    keep = m.debug_buffer("crop_keep")
+    assert 0 < keep.sum() < keep.size
+    assert (pos.reshape(B, -1, 3) - ref).abs().max() < 2e-3
+
+
+def sidechain_pred_under_crop_case(make, place):
+    """sidechain_pred with crop_beyond: the reference crops the graph first and returns rows for the KEPT residues only
+    (utils/utils.py:388-413, models/cg_model.py:397-402); the library's node table still holds every residue, so
+    MIScoreModel.__call__ compacts the rows through the device's crop mask.  And ddmi_sidechain_pred belongs to the ddmi_forward
+    directly before it: after a sampling loop on the same handle it raises instead of reading that pass's table."""
+    from diffdock_amd import lib as _l
+    from diffdock_amd.lib import DdmiError
+    from oracle.sampling import crop_beyond
+    from util import fixture_case
+    fs, cfg, data_list = fixture_case("tiny_sidechain")
+    m = make(cfg, fs["state_dict"])
+    d = torch.cdist(data_list[0]["ligand"].pos, data_list[0]["receptor"].pos).min(0).values
+    cutoff = float(d.sort().values[len(d) // 2]) + 1e-3      # about half of the residues of pose 0 survive
+    cropped = [crop_beyond(copy.deepcopy(g), cutoff) for g in data_list]
+    n_keep = sum(int(c["receptor"].pos.shape[0]) for c in cropped)
+    assert 0 < n_keep < sum(int(g["receptor"].pos.shape[0]) for g in data_list)
+    ob = HeteroBatch.from_data_list(cropped)
+    set_time(ob, 0.4, 0.4, 0.4, ob.num_graphs)
+    ref = oracle_model(cfg, fs["state_dict"], dtype=F64)(ob)
+    batch = HeteroBatch.from_data_list(data_list)
+    set_time(batch, 0.4, 0.4, 0.4, batch.num_graphs)
+    m.set_crop_cutoff(cutoff)
+    out = m(place(batch))
+    m.set_crop_cutoff(None)
+    assert out[3].shape == ref[3].shape == (n_keep, 10)
+    assert_scores_close(out[:4], ref[:4], names=("tr", "rot", "tor", "sidechain"), what="sidechain under crop")
+    # a sampling loop in between: the table of its last step is not what ddmi_sidechain_pred may read
+    sched = get_t_schedule(2)
+    m.sample_batch(place(batch), 2, (sched, sched, sched), seed=1, sample_ids=list(range(batch.num_graphs)), no_final_step_noise=True)
+    side = place(torch.empty(int(batch["receptor"].pos.shape[0]), 10))
+    with pytest.raises(DdmiError):
+        _l.check(m.lib, m.lib.ddmi_sidechain_pred(m._h, side.data_ptr(), None))

@@ -13,6 +13,8 @@ from diffdock_amd.hetero import HeteroBatch, set_time
 from diffdock_amd.model import MIScoreModel
 from oracle.cg_model import CGModelOracle
 from oracle.conformer import get_t_schedule
+
+import cases
 from util import assert_scores_close, fixture_case, graph_from_dict, load_fixture, oracle_model, rel_err, split_draws, tables
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -31,6 +33,14 @@ def emu_lib():
     r = subprocess.run(["make", "-j8", "-C", os.path.join(ROOT, "diffdock_amd", "csrc"), "emu"], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     return EMU
+
+
+def emu_make(emu_lib):
+    return lambda cfg, sd: make_model(cfg, sd, emu_lib)
+
+
+def emu_place(x):
+    return x
 
 
 def make_model(cfg, sd, emu_lib):
@@ -101,84 +111,21 @@ def test_modify_conformer_matches_reference(emu_lib):
 def test_no_cross_edges_and_ragged_batch(emu_lib):
     """Edge cases the reference handles (with e3nn tensor products): a ligand out of cross-graph range
     (empty cross groups) and a batch of two DIFFERENT complexes (ragged sizes)."""
-    from diffdock_amd.config import TINY
-    from diffdock_amd.synth import make_complex
-    from diffdock_amd.weights import init_state_dict
-    cfg = TINY.replace(sh_lmax=2)
-    sd = init_state_dict(cfg, seed=5)
-    g1, g2 = make_complex(seed=11, n_res=24, n_lig=9), make_complex(seed=12, n_res=31, n_lig=13)
-    g1["ligand"].pos = g1["ligand"].pos + torch.tensor([[500.0, 0.0, 0.0]])   # far away: no cross edges for graph 0
-    batch = HeteroBatch.from_data_list([g1, g2])
-    set_time(batch, 0.4, 0.4, 0.4, 2)
-    so3_t, tor_t = tables()
-    ref = CGModelOracle(cfg, sd, so3_t, tor_t)(batch)
-    m = make_model(cfg, sd, emu_lib)
-    out = m(batch)
-    for a, b in zip(out[:3], ref[:3]):
-        assert rel_err(a, b) < 1e-4
-    g2["ligand"].pos = g2["ligand"].pos + torch.tensor([[0.0, 700.0, 0.0]])    # now NO cross edges at all
-    batch = HeteroBatch.from_data_list([g1, g2])
-    set_time(batch, 0.4, 0.4, 0.4, 2)
-    ref = CGModelOracle(cfg, sd, so3_t, tor_t)(batch)
-    out = make_model(cfg, sd, emu_lib)(batch)
-    assert int(m.debug_buffer("offs_l")[-1]) >= 0
-    for a, b in zip(out[:3], ref[:3]):
-        assert rel_err(a, b) < 1e-4
+    cases.no_cross_edges_and_ragged_batch_case(emu_make(emu_lib), emu_place)
 
 
 @pytest.mark.parametrize("no_torsion", [False, True])
 def test_rigid_ligand_and_no_torsion_early_out(no_torsion, emu_lib):
     """cg_model.py:404: a ligand without rotatable bonds, or `no_torsion`, returns (tr, rot, empty(0), None); the device loop
     then runs the rigid-body update only (modify_conformer_batch with zero torsions)."""
-    from diffdock_amd.config import TINY
-    from diffdock_amd.synth import make_complex, make_pose_list
-    from diffdock_amd.weights import init_state_dict
-    cfg = TINY.replace(no_torsion=no_torsion)
-    sd = init_state_dict(cfg, seed=5)
-    g = make_complex(seed=11, n_res=20, n_lig=8)
-    if not no_torsion:
-        g["ligand"].edge_mask = torch.zeros_like(g["ligand"].edge_mask)
-        g["ligand"].mask_rotate = [g["ligand"].mask_rotate[0][:0]]
-    dl = make_pose_list(g, 2, tr_sigma_max=cfg.tr_sigma_max, seed=3, no_torsion=no_torsion)
-    b = HeteroBatch.from_data_list(dl)
-    set_time(b, 0.5, 0.5, 0.5, 2)
-    so3_t, tor_t = tables()
-    ref = CGModelOracle(cfg, sd, so3_t, tor_t)(b)
-    m = make_model(cfg, sd, emu_lib)
-    tr, rot, tor, none = m(b)
-    assert none is None and ref[3] is None and tor.shape == (0,) and ref[2].shape == (0,)
-    assert rel_err(tr, ref[0]) < 1e-4 and rel_err(rot, ref[1]) < 1e-4
-    sched = get_t_schedule(3)
-    start = b["ligand"].pos.clone()
-    pos = m.sample_batch(b, 3, (sched, sched, sched), seed=1, no_final_step_noise=True)
-    assert pos.shape == start.shape and torch.isfinite(pos).all()
-    # rigid motion only: the intramolecular distances of every pose are those of the start conformer
-    for k in range(2):
-        a0, a1 = start.reshape(2, -1, 3)[k], pos.reshape(2, -1, 3)[k]
-        assert (torch.cdist(a0, a0) - torch.cdist(a1, a1)).abs().max() < 1e-3
+    cases.rigid_ligand_case(emu_make(emu_lib), emu_place, no_torsion)
 
 
 @pytest.mark.parametrize("n_res,n_lig,B", [(20, 8, 1), (3, 4, 2), (40, 2, 3)])
 def test_degenerate_sizes(n_res, n_lig, B, emu_lib):
     """A batch of one pose, a 3-residue receptor (fewer neighbours than the 24-nearest graph asks for), a 2-atom ligand:
     forward against the oracle, and the device loop stays finite."""
-    from diffdock_amd.config import TINY
-    from diffdock_amd.synth import make_complex, make_pose_list
-    from diffdock_amd.weights import init_state_dict
-    cfg = TINY
-    sd = init_state_dict(cfg, seed=5)
-    g = make_complex(seed=11, n_res=n_res, n_lig=n_lig)
-    b = HeteroBatch.from_data_list(make_pose_list(g, B, tr_sigma_max=cfg.tr_sigma_max, seed=3))
-    set_time(b, 0.5, 0.5, 0.5, B)
-    so3_t, tor_t = tables()
-    ref = CGModelOracle(cfg, sd, so3_t, tor_t)(b)
-    m = make_model(cfg, sd, emu_lib)
-    out = m(b)
-    for o, r in zip(out[:3], ref[:3]):
-        assert o.shape == r.shape and (r.numel() == 0 or rel_err(o, r) < 1e-4)
-    sched = get_t_schedule(3)
-    pos = m.sample_batch(b, 3, (sched, sched, sched), seed=1, no_final_step_noise=True)
-    assert pos.shape == b["ligand"].pos.shape and torch.isfinite(pos).all()
+    cases.degenerate_sizes_case(emu_make(emu_lib), emu_place, n_res, n_lig, B)
 
 
 def test_errors_are_python_exceptions(emu_lib):
@@ -211,24 +158,8 @@ def test_errors_are_python_exceptions(emu_lib):
 
 def test_crop_with_embedding_layers_matches_oracle(emu_lib):
     """crop_beyond + receptor embedding layers: the reference re-embeds the CROPPED receptor each step."""
-    from oracle.sampling import sampling as oracle_sampling
-    fx, cfg, data_list = fixture_case("tiny_l1_1group_emb")
-    cfg = cfg.replace(crop_beyond=9.0)
-    so3_t, tor_t = tables()
-    B, R = len(data_list), int(data_list[0]["ligand"].edge_mask.sum())
-    g = torch.Generator().manual_seed(1)
-    steps = 3
-    noise = (torch.randn(steps, B, 3, generator=g), torch.randn(steps, B, 3, generator=g), torch.randn(steps, B * R, generator=g))
-    ref = oracle_sampling([d.clone() for d in data_list], CGModelOracle(cfg, fx["state_dict"], so3_t, tor_t), steps, cfg, noise,
-                          batch_size=B, no_final_step_noise=True)
-    ref = torch.stack([d["ligand"].pos for d in ref])
-    m = make_model(cfg, fx["state_dict"], emu_lib)
-    sched = get_t_schedule(steps)
-    pos = m.sample_batch(HeteroBatch.from_data_list(data_list), steps, (sched, sched, sched), noise=noise,
-                         no_final_step_noise=True, crop_beyond=cfg.crop_beyond)
-    keep = m.debug_buffer("crop_keep")
-    assert 0 < keep.sum() < keep.size
-    assert (pos.reshape(B, -1, 3) - ref).abs().max() < 2e-3
+    cases.crop_with_embedding_layers_case(emu_make(emu_lib), emu_place)
+
 
 @pytest.mark.parametrize("lmax", [1, 2])
 def test_fused_conv_full_width_matches_oracle(lmax, emu_lib, monkeypatch):
@@ -236,36 +167,7 @@ def test_fused_conv_full_width_matches_oracle(lmax, emu_lib, monkeypatch):
     (chain shapes (12,3,3,3)/(3,3,3,3)/(12,-,-,-) and the packed 12|3x3 granule of the second layer), the generic variant at
     sh_lmax=2, receptor residues with more than 32 ligand neighbours (two virtual nodes per residue), against the oracle, with
     the dense-row and the sparse-row loop."""
-    from dataclasses import replace
-    from diffdock_amd.config import DDL_SYNTH
-    from diffdock_amd.synth import make_complex, make_pose_list
-    from diffdock_amd.weights import init_state_dict
-    cfg = replace(DDL_SYNTH, num_conv_layers=2, sh_lmax=lmax, lm_embedding_type=None, dynamic_max_cross=False,
-                  cross_max_distance=80.0, tr_sigma_max=5.0)
-    sd = init_state_dict(cfg, seed=3)
-    g = make_complex(seed=1, n_res=12, n_lig=40, lm_dim=0)
-    dl = make_pose_list(g, 2, tr_sigma_max=cfg.tr_sigma_max, seed=5, initial_noise_std_proportion=0.3)
-    b = HeteroBatch.from_data_list(dl)
-    set_time(b, 0.6, 0.6, 0.6, b.num_graphs)
-    so3_t, tor_t = tables()
-    ref = CGModelOracle(cfg, sd, so3_t, tor_t)(b)[:3]
-    outs = {}
-    for dense in ("1", "0"):          # dense-row and sparse-row loops (lmax 2: the generic, compiler-scheduled variant both times)
-        monkeypatch.setenv("DDMI_FUSED_DENSE", dense)
-        m = make_model(cfg, sd, emu_lib)
-        m.set_kernel_timing(True)
-        outs[dense] = m(b)[:3]
-        assert "k_conv_fused" in m.kernel_timings()
-        assert int(m.debug_buffer("vn_off_cross")[-1]) == 2 * b["receptor"].pos.shape[0]   # 40 neighbours -> 2 virtual nodes
-        for o, r in zip(outs[dense], ref):
-            assert rel_err(o, r) < 1e-4
-    for a_, b_ in zip(outs["1"], outs["0"]):
-        assert rel_err(a_, b_) < 1e-5
-    if lmax == 1:   # the merged first-layer granule (three scalar channel tiles in one) against the separate granules
-        monkeypatch.setenv("DDMI_FUSED_TRI", "0")
-        sep = make_model(cfg, sd, emu_lib)(b)[:3]
-        for a_, b_ in zip(outs["0"], sep):
-            assert rel_err(a_, b_) < 1e-5
+    cases.fused_conv_full_width_case(emu_make(emu_lib), emu_place, monkeypatch.setenv, lmax)
 
 
 def test_packed_granules_match_oracle_and_classic_granules(emu_lib, monkeypatch, capfd):
@@ -305,31 +207,7 @@ def test_packing_is_dropped_in_layers_with_generic_granules(ns, emu_lib, monkeyp
     """ns = 16 / 32 with nv = 10: the 4- / 8-step scalar chains are outside the static shape set, so every layer with a scalar
     input path runs the predicated kernel variant, which walks classic 4-slot granules only.  Such a layer must not contain a
     packed granule (round-3 defect: its slots 4..6 were dropped, 1 % error in the 1e block); packing on / off must agree."""
-    from dataclasses import replace
-    from diffdock_amd.config import DDL_SYNTH
-    from diffdock_amd.synth import make_complex, make_pose_list
-    from diffdock_amd.weights import init_state_dict
-    cfg = replace(DDL_SYNTH, ns=ns, nv=10, num_conv_layers=4, lm_embedding_type=None, dynamic_max_cross=False, cross_max_distance=80.0,
-                  tr_sigma_max=5.0)
-    sd = init_state_dict(cfg, seed=3)
-    g = make_complex(seed=1, n_res=10, n_lig=12, lm_dim=0)
-    b = HeteroBatch.from_data_list(make_pose_list(g, 2, tr_sigma_max=cfg.tr_sigma_max, seed=5, initial_noise_std_proportion=0.3))
-    set_time(b, 0.6, 0.6, 0.6, b.num_graphs)
-    ref = CGModelOracle(cfg, sd, *tables())(b)[:3]
-    outs = {}
-    monkeypatch.setenv("DDMI_DEBUG_GRAN", "1")
-    for pack in ("1", "0"):
-        monkeypatch.setenv("DDMI_FUSED_PACK", pack)
-        capfd.readouterr()
-        m = make_model(cfg, sd, emu_lib)
-        for line in capfd.readouterr().err.splitlines():
-            if line.startswith("ddmi granules") and "[shape 0 " in line:
-                assert not any(f"[shape {s} " in line for s in (4, 5, 6, 7)), line
-        outs[pack] = m(b)[:3]
-        for o, r in zip(outs[pack], ref):
-            assert rel_err(o, r) < 1e-5
-    for a_, b_ in zip(outs["1"], outs["0"]):
-        assert rel_err(a_, b_) < 1e-5
+    cases.packing_dropped_case(emu_make(emu_lib), emu_place, monkeypatch.setenv, ns, listing=lambda: capfd.readouterr().err)
 
 
 def test_shared_node_contraction_matches_oracle(emu_lib, monkeypatch):
@@ -337,27 +215,7 @@ def test_shared_node_contraction_matches_oracle(emu_lib, monkeypatch):
     granules contract them on the 4x4x1 MFMA, packed granules read their rows through the slot map), forced onto EVERY edge
     group (DDMI_FUSED_SHARED=2 with dense rows): tiles with 16 distinct nodes (four passes), tiles that mix nodes with one and
     several virtual nodes, the bias row, against the oracle and against the per-virtual-node form."""
-    from dataclasses import replace
-    from diffdock_amd.config import DDL_SYNTH
-    from diffdock_amd.synth import make_complex, make_pose_list
-    from diffdock_amd.weights import init_state_dict
-    cfg = replace(DDL_SYNTH, num_conv_layers=4, lm_embedding_type=None, dynamic_max_cross=False, cross_max_distance=80.0, tr_sigma_max=5.0)
-    sd = init_state_dict(cfg, seed=3)
-    g = make_complex(seed=2, n_res=75, n_lig=7, lm_dim=0)     # 75 receptor neighbours per ligand atom: 32 + 32 + 11 edges
-    b = HeteroBatch.from_data_list(make_pose_list(g, 2, tr_sigma_max=cfg.tr_sigma_max, seed=5, initial_noise_std_proportion=0.3))
-    set_time(b, 0.6, 0.6, 0.6, b.num_graphs)
-    ref = CGModelOracle(cfg, sd, *tables())(b)[:3]
-    monkeypatch.setenv("DDMI_FUSED_DENSE", "2")
-    outs = {}
-    for shared in ("2", "1", "0"):
-        monkeypatch.setenv("DDMI_FUSED_SHARED", shared)
-        m = make_model(cfg, sd, emu_lib)
-        outs[shared] = m(b)[:3]
-        for o, r in zip(outs[shared], ref):
-            assert rel_err(o, r) < 1e-4, shared
-    for k in ("2", "1"):
-        for a_, b_ in zip(outs[k], outs["0"]):
-            assert rel_err(a_, b_) < 1e-5
+    cases.shared_node_contraction_case(emu_make(emu_lib), emu_place, monkeypatch.setenv)
 
 
 def test_split_bf16_edge_product_matches_f32_route_and_oracle(emu_lib, monkeypatch):
@@ -397,70 +255,21 @@ def test_in_tile_pre_reduction_of_lig_rec_messages(emu_lib, monkeypatch):
     rows flagged live (tensor_layers.py:144,220-221: the scatter-mean itself is unchanged -- counts are the true edge counts).
     3 poses x 12 residues x 20 atoms: tiles 0 and 1 straddle two poses (targets span 40 rows: one row per edge as before), tile 2
     is pre-reduced.  Against the oracle and against the per-edge route (DDMI_FUSED_PRERED=0)."""
-    from dataclasses import replace
-    from diffdock_amd.config import DDL_SYNTH
-    from diffdock_amd.synth import make_complex, make_pose_list
-    from diffdock_amd.weights import init_state_dict
-    cfg = replace(DDL_SYNTH, num_conv_layers=4, lm_embedding_type=None, dynamic_max_cross=False, cross_max_distance=80.0, tr_sigma_max=5.0)
-    sd = init_state_dict(cfg, seed=3)
-    g = make_complex(seed=1, n_res=12, n_lig=20, lm_dim=0)
-    b = HeteroBatch.from_data_list(make_pose_list(g, 3, tr_sigma_max=cfg.tr_sigma_max, seed=5, initial_noise_std_proportion=0.3))
-    set_time(b, 0.6, 0.6, 0.6, b.num_graphs)
-    ref = CGModelOracle(cfg, sd, *tables())(b)[:3]
-    outs = {}
-    for pre in ("1", "0"):
-        monkeypatch.setenv("DDMI_FUSED_PRERED", pre)
-        m = make_model(cfg, sd, emu_lib)
-        outs[pre] = m(b)[:3]
-        if pre == "1":
-            hdr = m.debug_buffer("prered_tile_hdr")
-            assert hdr[:3, 0].tolist() == [0, 0, 1] and hdr[2, 1:3].tolist() == [40, 20]   # (mode, first target row, span)
-            assert (hdr[2, 4:24] >= 0).all() and (hdr[2, 24:36] == -1).all()            # one message row per target of the tile
-        for o, r in zip(outs[pre], ref):
-            assert rel_err(o, r) < 1e-4
-    for a_, b_ in zip(outs["1"], outs["0"]):
-        assert rel_err(a_, b_) < 1e-5
+    cases.in_tile_pre_reduction_case(emu_make(emu_lib), emu_place, monkeypatch.setenv)
 
 
 @pytest.mark.parametrize("name", ["tiny_l1", "tiny_l2"])
 def test_readout_tensor_product_forms_agree(name, emu_lib, monkeypatch):
     """final_conv / tor_bond_conv in the direct (per-edge-weight) form: the wave-per-item, thread-per-item and
     workgroup-per-edge kernels (k_readout.hip; picked by launch size in production, forced here) against the reference fixture."""
-    fx, cfg, data_list = fixture_case(name)
-    batch = HeteroBatch.from_data_list(data_list)
-    set_time(batch, fx["t"], fx["t"], fx["t"], batch.num_graphs)
-    ref = fx["forward"]
-    for form in ("edge", "thread", "wave"):
-        monkeypatch.setenv("DDMI_TP_APPLY", form)
-        m = make_model(cfg, fx["state_dict"], emu_lib)
-        tr, rot, tor, _ = m(batch)
-        assert_scores_close((tr, rot, tor), (ref["tr"], ref["rot"], ref["tor"]), what=form)
+    cases.readout_tensor_product_forms_case(emu_make(emu_lib), emu_place, monkeypatch.setenv, name)
 
 
 def test_ligand_atoms_with_many_receptor_neighbours(emu_lib):
     """Ligand-gather groups through the fused kernel with several virtual nodes per ligand atom (70 receptor neighbours ->
     32 + 32 + 6 edges: the node term is repeated per virtual node, the last one is a sparse tile) at a width the MFMA first
     layer and the dense-row loop accept (ns = 16), against the oracle."""
-    from diffdock_amd.config import TINY
-    from diffdock_amd.synth import make_complex, make_pose_list
-    from diffdock_amd.weights import init_state_dict
-    cfg = TINY.replace(ns=16, nv=4, sh_lmax=1, num_conv_layers=3, dynamic_max_cross=False, cross_max_distance=200.0,
-                       lm_embedding_type=None)
-    sd = init_state_dict(cfg, seed=9)
-    g = make_complex(seed=21, n_res=70, n_lig=5, lm_dim=0)
-    b = HeteroBatch.from_data_list(make_pose_list(g, 2, tr_sigma_max=cfg.tr_sigma_max, seed=4))
-    set_time(b, 0.5, 0.5, 0.5, 2)
-    so3_t, tor_t = tables()
-    ref = CGModelOracle(cfg, sd, so3_t, tor_t)(b)[:3]
-    m = make_model(cfg, sd, emu_lib)
-    m.set_kernel_timing(True)
-    out = m(b)[:3]
-    launched = m.kernel_timings()
-    assert "k_conv_fused" in launched
-    assert int(m.debug_buffer("vn_off_rl")[-1]) == 3 * b["ligand"].pos.shape[0]     # ceil(70 / 32) virtual nodes per ligand atom
-    assert int(m.debug_buffer("vn_off_cross")[-1]) == b["receptor"].pos.shape[0]    # 5 ligand neighbours: one sparse tile each
-    for o, r in zip(out, ref):
-        assert rel_err(o, r) < 1e-4
+    cases.many_receptor_neighbours_case(emu_make(emu_lib), emu_place)
 
 
 @pytest.mark.parametrize("name", ["tiny_conf_l2", "tiny_conf_aa_l1", "tiny_conf_atom"])
@@ -599,63 +408,14 @@ def test_sidechain_pred_under_a_device_crop_and_after_other_passes(emu_lib):
     (utils/utils.py:388-413, models/cg_model.py:397-402); the library's node table still holds every residue, so
     MIScoreModel.__call__ compacts the rows through the device's crop mask.  And ddmi_sidechain_pred belongs to the ddmi_forward
     directly before it: after a sampling loop on the same handle it raises instead of reading that pass's table."""
-    import copy
-    from diffdock_amd.lib import DdmiError
-    from oracle.sampling import crop_beyond
-    fs, cfg, data_list = fixture_case("tiny_sidechain")
-    m = make_model(cfg, fs["state_dict"], emu_lib)
-    d = torch.cdist(data_list[0]["ligand"].pos, data_list[0]["receptor"].pos).min(0).values
-    cutoff = float(d.sort().values[len(d) // 2]) + 1e-3      # about half of the residues of pose 0 survive
-    cropped = [crop_beyond(copy.deepcopy(g), cutoff) for g in data_list]
-    n_keep = sum(int(c["receptor"].pos.shape[0]) for c in cropped)
-    assert 0 < n_keep < sum(int(g["receptor"].pos.shape[0]) for g in data_list)
-    ob = HeteroBatch.from_data_list(cropped)
-    set_time(ob, 0.4, 0.4, 0.4, ob.num_graphs)
-    ref = oracle_model(cfg, fs["state_dict"])(ob)
-    batch = HeteroBatch.from_data_list(data_list)
-    set_time(batch, 0.4, 0.4, 0.4, batch.num_graphs)
-    m.set_crop_cutoff(cutoff)
-    out = m(batch)
-    m.set_crop_cutoff(None)
-    assert out[3].shape == ref[3].shape == (n_keep, 10)
-    assert rel_err(out[3], ref[3]) < 1e-4
-    for o, r in zip(out[:3], ref[:3]):
-        assert rel_err(o, r) < 1e-4
-    # a sampling loop in between: the table of its last step is not what ddmi_sidechain_pred may read
-    sched = get_t_schedule(2)
-    m.sample_batch(batch, 2, (sched, sched, sched), seed=1, sample_ids=list(range(batch.num_graphs)), no_final_step_noise=True)
-    side = torch.empty(int(batch["receptor"].pos.shape[0]), 10)
-    with pytest.raises(DdmiError):
-        from diffdock_amd import lib as _l
-        _l.check(m.lib, m.lib.ddmi_sidechain_pred(m._h, side.data_ptr(), None))
+    cases.sidechain_pred_under_crop_case(emu_make(emu_lib), emu_place)
 
 
 def test_all_atom_ragged_batch_and_empty_ligand_atom_group(emu_lib):
     """AAModel on a batch of two DIFFERENT complexes (residue / atom / ligand counts differ), first with one ligand out of
     reach of every receptor atom, then with the ligand<->atom group completely empty (the reference's FasterTensorProduct
     cannot run that; sh_lmax = 2 can), against the oracle."""
-    from diffdock_amd.config import TINY
-    from diffdock_amd.synth import make_complex, make_pose_list
-    from diffdock_amd.weights import init_state_dict
-    cfg = TINY.replace(all_atoms=True, sh_lmax=2, num_conv_layers=3, dynamic_max_cross=False, cross_max_distance=60.0)
-    sd = init_state_dict(cfg, seed=2)
-    g1 = make_complex(seed=31, n_res=14, n_lig=7, all_atoms=True, atoms_per_res=(2, 5))
-    g2 = make_complex(seed=32, n_res=19, n_lig=11, all_atoms=True, atoms_per_res=(2, 5))
-    d1 = make_pose_list(g1, 1, tr_sigma_max=5.0, seed=1, initial_noise_std_proportion=0.05)[0]
-    d2 = make_pose_list(g2, 1, tr_sigma_max=5.0, seed=2, initial_noise_std_proportion=0.05)[0]
-    d2["ligand"].pos = d2["ligand"].pos + torch.tensor([30.0, 0.0, 0.0])
-    m = make_model(cfg, sd, emu_lib)
-    for empty in (False, True):
-        if empty:
-            d1["ligand"].pos = d1["ligand"].pos + torch.tensor([0.0, 40.0, 0.0])
-        batch = HeteroBatch.from_data_list([d1, d2])
-        set_time(batch, 0.5, 0.5, 0.5, 2)
-        ref = oracle_model(cfg, sd)(batch, return_intermediates=True)
-        assert (ref[4]["edge_counts"][2] == 0) == empty
-        out = m(batch)
-        assert int(m.debug_buffer("offs_la_l")[-1]) == ref[4]["edge_counts"][2]
-        for o, r in zip(out[:3], ref[:3]):
-            assert rel_err(o, r) < 1e-4
+    cases.all_atom_ragged_batch_case(emu_make(emu_lib), emu_place)
 
 
 def test_tile_per_pose_makes_shards_bit_identical(emu_lib):
@@ -779,50 +539,7 @@ def test_fused_node_update_matches_separate_launches(emu_lib):
     the node tables are the same sums in the same order -- layer 1's table, which no fused P / Q has touched yet, is bit-identical --
     and the scores agree at rounding level (P / Q take a 48-term fp32 sum in another order) and with the oracle.  With the per-step
     crop (its own reduce-group list), sidechain rows (the last layer reduces every row), a ragged batch of two complexes."""
-    from dataclasses import replace
-    from diffdock_amd.config import DDL_SYNTH
-    from diffdock_amd.synth import make_complex, make_pose_list
-    from diffdock_amd.weights import init_state_dict
-    cfg = replace(DDL_SYNTH, num_conv_layers=3, lm_embedding_type=None, dynamic_max_cross=False, cross_max_distance=80.0, tr_sigma_min=0.1,
-                  tr_sigma_max=0.5, sidechain_pred=True)
-    sd = init_state_dict(cfg, seed=3)
-    g1 = make_complex(seed=4, n_res=19, n_lig=10, lm_dim=0)
-    g2 = make_complex(seed=5, n_res=13, n_lig=7, lm_dim=0)
-    dl = make_pose_list(g1, 2, tr_sigma_max=5.0, seed=6, initial_noise_std_proportion=0.3) + make_pose_list(g2, 1, tr_sigma_max=5.0, seed=7, initial_noise_std_proportion=0.3)
-    sched = get_t_schedule(1)
-    res = {}
-    # (fused = four waves per node at this size; fused16 = the sixteen-nodes-per-workgroup shape of chip-filling batches; fused + grouped
-    # dispatch: GPU route test)
-    for key, opts in (("separate", ()), ("fused", (("node_update", 1),)), ("fused16", (("node_update", 2),))):
-        m = make_model(cfg.replace(exec_options=opts), sd, emu_lib)
-        b = HeteroBatch.from_data_list(dl)
-        set_time(b, 0.6, 0.6, 0.6, b.num_graphs)
-        m.set_kernel_timing(True)
-        out = [o.clone() for o in m(b)]
-        timers = m.kernel_timings()
-        m.set_kernel_timing(False)
-        x1 = torch.from_numpy(m.debug_buffer("x1").copy())
-        cropped, traj = None, None
-        if key != "fused16":
-            m.set_crop_cutoff(6.0)
-            cropped = [o.clone() for o in m(b)]
-            m.set_crop_cutoff(None)
-            traj = m.sample_batch(HeteroBatch.from_data_list(dl[:2]), 1, (sched, sched, sched), seed=11, sample_ids=[0, 1], no_final_step_noise=True).clone()
-        res[key] = (out, x1, cropped, traj, timers)
-    # launches of the first-Linear GEMMs per forward: per layer and group before, the first layer's batch + the sigma batch now
-    assert res["fused"][4]["conv_fc1_gemms"][1] == 2
-    assert res["separate"][4]["conv_fc1_gemms"][1] > 2
-    assert torch.equal(res["fused16"][0][0], res["fused"][0][0]) and torch.equal(res["fused16"][0][2], res["fused"][0][2])   # same sums, same MFMA chains
-    for key in ("fused", "fused16"):
-        assert torch.equal(res[key][1], res["separate"][1])          # first interaction layer's node table
-        for a_, b_ in zip(res[key][0], res["separate"][0]):
-            assert rel_err(a_, b_) < 1e-5
-        if res[key][2] is not None:
-            for a_, b_ in zip(res[key][2], res["separate"][2]):
-                assert a_.shape == b_.shape and rel_err(a_, b_) < 1e-5
-            assert (res[key][3] - res["separate"][3]).abs().max() < 1e-4
-    b = HeteroBatch.from_data_list(dl)
-    set_time(b, 0.6, 0.6, 0.6, b.num_graphs)
-    ref = CGModelOracle(cfg, sd, *tables())(b)
-    for o, r in zip(res["fused"][0][:3], ref[:3]):
-        assert rel_err(o, r) < 1e-4
+    # (node_update 3, the four-waves-per-node shape forced, and the bf16x4 edge product: tests/test_gpu_edges.py)
+    cases.fused_node_update_case(emu_make(emu_lib), emu_place, modes=(1, 2))
+
+

@@ -16,7 +16,7 @@ from diffdock_amd.synth import make_complex, make_pose_list
 from diffdock_amd.weights import init_state_dict
 from oracle.cg_model import CGModelOracle
 from oracle.conformer import get_t_schedule
-from util import assert_scores_close, fixture_case, graph_from_dict, load_fixture, oracle_model, rel_err, split_draws, tables
+from util import assert_scores_close, elem_excess, fixture_case, graph_from_dict, load_fixture, oracle_model, rel_err, split_draws, tables
 
 pytestmark = pytest.mark.gpu
 REL = 1e-4
@@ -59,7 +59,8 @@ def test_forward_matches_reference_fixture(name):
         for l, ref_nodes in enumerate(ref["conv_out"]):
             mine = torch.from_numpy(m.debug_buffer(f"x{l + 1}"))
             n = ref_nodes.shape[0] if l < len(ref["conv_out"]) - 1 else batch["ligand"].pos.shape[0]
-            assert rel_err(mine[:n, :ref_nodes.shape[1]], ref_nodes[:n]) < REL, l
+            mine = mine[:n, :ref_nodes.shape[1]]
+            assert rel_err(mine, ref_nodes[:n]) < REL and elem_excess(mine, ref_nodes[:n]) <= 1.0, l
 
 
 @pytest.mark.parametrize("name", ["tiny_l1", "tiny_l2", "tiny_l2_crop", "tiny_aa_l1", "tiny_aa_l2", "tiny_aa_l2_emb", "tiny_2nd", "tiny_aa_2nd", "tiny_fourier",
@@ -149,6 +150,7 @@ def test_selectable_kernel_paths_agree_on_the_gpu(env, width48_case, monkeypatch
     assert "k_conv_fused" in launched
     for o, b, r in zip(out, base, ref):
         assert rel_err(o.cpu(), r) < REL and rel_err(o.cpu(), b) < 1e-5
+        assert elem_excess(o.cpu(), r) <= 1.0
 
 
 @pytest.mark.parametrize("name", ["tiny_conf_l2", "tiny_conf_aa_l1", "tiny_conf_atom"])
@@ -229,7 +231,8 @@ def test_all_atom_ddl_width_matches_oracle():
     for l in range(cfg.num_conv_layers - 1):   # all node rows: ligand, residues, atoms
         mine = torch.from_numpy(m.debug_buffer(f"x{l + 1}"))
         ref = inter[f"node_attr{l + 1}"]
-        assert rel_err(mine[:, :ref.shape[1]], ref) < REL, l
+        mine = mine[:, :ref.shape[1]]
+        assert rel_err(mine, ref) < REL and elem_excess(mine, ref) <= 1.0, l
 
 
 def test_all_atom_bench_size_complex_matches_oracle():
@@ -251,7 +254,8 @@ def test_all_atom_bench_size_complex_matches_oracle():
     for l in range(cfg.num_conv_layers - 1):
         mine = torch.from_numpy(m.debug_buffer(f"x{l + 1}"))
         ref = inter[f"node_attr{l + 1}"]
-        assert rel_err(mine[:, :ref.shape[1]], ref) < REL, l
+        mine = mine[:, :ref.shape[1]]
+        assert rel_err(mine, ref) < REL and elem_excess(mine, ref) <= 1.0, l
 
 
 def test_full_size_properties():
