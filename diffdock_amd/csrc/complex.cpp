@@ -16,6 +16,10 @@ struct Model::Cx {
   int B = 0, nL = 0, nR = 0, N = 0, Eb = 0, Err = 0, nT = 0;
   int maxNl = 0, maxNr = 0, Ell_cap = 0, Elr_cap = 0, tor_cap = 32, Et = 0, lig_cap = 33;
   bool uniform = false; int Nl_one = 0, R_one = 0;
+  // every graph's receptor is a bitwise copy of graph 0's (node count, features, positions, contact graph offset by the graph):
+  // under one t for all graphs the layer-0 rec-rec messages are the same for every graph (forward, exec.rec_share)
+  bool rec_copies = false; int Rc_one = 0, Erc_one = 0;   // residues / rec-rec edges of one copy
+  ReduceGroup* rg_all_share = nullptr;                    // rg_all with the rec-rec entry folded onto graph 0 (tmod = Rc_one)
   std::vector<int> lig_ptr_h, rec_ptr_h;
   // static
   int *lig_batch, *rec_batch, *lig_ptr, *rec_ptr, *lig_x;
@@ -48,12 +52,14 @@ struct Model::Cx {
                  float* rows = nullptr;   // per-edge rows of k_conv_fused (k_vn_rows)
                  int* tile_hdr = nullptr; unsigned char* live = nullptr;   // in-tile pre-reduction (launch_vn_tiles): tile headers, rows that get written
                  int* nvn_pad = nullptr;   // tile_per_pose: length of the list with every graph padded to whole tiles (else voff[gcount])
+                 int graphs = 0;           // graphs the gather nodes of the list span (tile_per_pose padding)
                  // what the lists and per-edge rows were built from (k_vn_rows bakes target slots, attribute rows, harmonics with
                  // their sign and edge weights in): a group that reuses a list id with any other input rebuilds it
                  const int *built_goff = nullptr, *built_tgt = nullptr, *built_tslot = nullptr, *built_arow = nullptr;
                  const float *built_nvec = nullptr, *built_ew = nullptr; float built_sgn = 0.f; int built_tbase = -1; long epoch = -1; };
   bool prered = false;   // the lig<-rec group (list 0) leaves one message row per (tile, target) instead of one per edge
-  VnSet vn[9];           // + 2 = ligand-ligand, 3 = rec<-lig (ligand gather nodes); all_atoms: 4 la, 5 ra, 6 aa, 7 al, 8 ar
+  VnSet vn[10];          // + 2 = ligand-ligand, 3 = rec<-lig (ligand gather nodes); all_atoms: 4 la, 5 ra, 6 aa, 7 al, 8 ar;
+                         // 9 = rec-rec of graph 0 only (rec_copies)
   // ---- all_atoms (models/aa_model.py): receptor heavy atoms = third node type, node rows [nL + nR, N)
   int nA = 0, maxNa = 0, Eaa = 0, Ear = 0, Ela_cap = 0;
   int *atom_batch = nullptr, *atom_ptr = nullptr, *atom_x = nullptr;
@@ -179,15 +185,19 @@ static VnRowsArgs vn_rows_args(const Model& m, const RunGroup& g) {
   vr.vcap = vs.vcap; vr.rows = vs.rows; vr.vn_ne = vs.ne;
   return vr;
 }
-static const char vn_type[9] = {'R', 'R', 'L', 'L', 'A', 'A', 'A', 'L', 'R'};   // gather-node type of every virtual-node list (set_complex)
+static const char vn_type[10] = {'R', 'R', 'L', 'L', 'A', 'A', 'A', 'L', 'R', 'R'};   // gather-node type of every virtual-node list (set_complex)
 // the stale lists of a layer's groups in two launches (+ the tile headers of the pre-reduced group)
 static void ensure_vn_all(Model& m, const std::vector<RunGroup>& groups, hipStream_t gs) {
   Cx& c = *m.cx;
   VnListsArgs LA;
   VnRowsArgs rows[VN_GROUPS_MAX];
+  const RunGroup* built[VN_GROUPS_MAX];
   const RunGroup* prered_g = nullptr;
   for (auto& g : groups) {
     if (vn_fresh(c, g) || g.gcount <= 0) continue;
+    bool queued = false;   // (a list is built once per launch even if two groups name it)
+    for (int i = 0; i < LA.n; ++i) queued = queued || built[i]->vn == g.vn;
+    if (queued) continue;
     DDMI_REQUIRE(LA.n < VN_GROUPS_MAX, DDMI_ERR_CAPACITY, "more edge groups than virtual-node list slots");
     Cx::VnSet& vs = c.vn[g.vn];
     VnListArgs& a = LA.g[LA.n];
@@ -196,15 +206,14 @@ static void ensure_vn_all(Model& m, const std::vector<RunGroup>& groups, hipStre
       const bool lig = vn_type[g.vn] == 'L', atom = vn_type[g.vn] == 'A';
       a.node_batch = lig ? c.lig_batch : atom ? c.atom_batch : c.rec_batch;
       a.graph_ptr = lig ? c.lig_ptr : atom ? c.atom_ptr : c.rec_ptr;
-      a.n_graphs = c.B; a.nvn_pad = vs.nvn_pad;
+      a.n_graphs = vs.graphs; a.nvn_pad = vs.nvn_pad;
     }
     rows[LA.n] = vn_rows_args(m, g);
     if (g.vn == 0 && c.prered) {
       prered_g = &g;
       if (m.cfg.sh_lmax <= 1) { rows[LA.n].tile_hdr = vs.tile_hdr; rows[LA.n].live = vs.live; }   // headers from the rows' own launch
     }
-    ++LA.n;
-    vn_mark_built(c, g);
+    built[LA.n++] = &g;
   }
   if (LA.n == 0) return;
   PhaseTimer t(m, "vn_build", gs);
@@ -213,6 +222,7 @@ static void ensure_vn_all(Model& m, const std::vector<RunGroup>& groups, hipStre
     Cx::VnSet& vs = c.vn[0];
     launch_vn_tiles(vs.nvn_pad ? vs.nvn_pad : vs.voff + prered_g->gcount, vs.vcap, vs.rows, vs.ne, vs.tile_hdr, vs.live, gs);
   }
+  for (int i = 0; i < LA.n; ++i) vn_mark_built(c, *built[i]);   // only once every launch went out (a throw leaves the lists stale)
 }
 static void ensure_vn(Model& m, const RunGroup& g, hipStream_t gs) {
   Cx& c = *m.cx;
@@ -225,7 +235,7 @@ static void ensure_vn(Model& m, const RunGroup& g, hipStream_t gs) {
     const bool lig = vn_type[g.vn] == 'L', atom = vn_type[g.vn] == 'A';
     pp.node_batch = lig ? c.lig_batch : atom ? c.atom_batch : c.rec_batch;
     pp.graph_ptr = lig ? c.lig_ptr : atom ? c.atom_ptr : c.rec_ptr;
-    pp.n_graphs = c.B; pp.nvn_pad = vs.nvn_pad;
+    pp.n_graphs = vs.graphs; pp.nvn_pad = vs.nvn_pad;
   }
   launch_vn_build(g.goff, g.gcount, vs.cnt, vs.voff, vs.node, vs.e0, vr, gs, vs.nvn_pad ? &pp : nullptr);
   if (g.vn == 0 && c.prered) launch_vn_tiles(vs.nvn_pad ? vs.nvn_pad : vs.voff + g.gcount, vs.vcap, vs.rows, vs.ne, vs.tile_hdr, vs.live, gs);
@@ -500,6 +510,7 @@ void run_conv(Model& m, const ConvW& L, const std::vector<RunGroup>& groups, con
                        L.has_bn ? L.bn_scale : nullptr, L.has_bn ? L.bn_bias : nullptr, L.residual ? 1 : 0, Xin, Xout, XS, s);
       return;
     }
+    DDMI_REQUIRE(rg_dev != c.rg_all_share, DDMI_ERR_STATE, "k_node_update does not fold message rows onto graph 0 (ReduceGroup::tmod)");
     PhaseTimer t(m, "k_reduce_bn", s);   // (same timer row: the scatter stage of the layer)
     NodeUpdateArgs a{};
     a.groups = rg_dev; a.n_groups = n_rg; a.nbase = nbase; a.ncount = ncount; a.D_in = L.D_in; a.D_out = L.D_out;
@@ -824,6 +835,22 @@ void set_complex(Model& m, const ddmi_complex& cc, hipStream_t s) {
     rr_tlist[rr_tslot[e]] = e;
     rr_gnode[e] = rr_dst[k];
   }
+  // batch of copies of one receptor (the poses of ddmi_sample): equal residue counts and the contact graph of every graph = graph 0's
+  // edge block offset by the graph (features and positions are compared on the device below, the flag read at the final sync)
+  bool copies = c.B > 1 && !cfg.all_atoms && !cfg.old_model && c.Err > 0 && c.Err % c.B == 0;
+  const int R1 = c.rec_ptr_h[1], E1 = copies ? c.Err / c.B : 0;
+  for (int b = 0; b < c.B && copies; ++b) copies = c.rec_ptr_h[b + 1] - c.rec_ptr_h[b] == R1;
+  for (int k = 0; k < c.Err && copies; ++k) {
+    const int q = k / E1, k0 = k - q * E1;
+    copies = rr_src[k] == rr_src[k0] + q * R1 && rr_dst[k] == rr_dst[k0] + q * R1 && rr_src[k0] < R1 && rr_dst[k0] < R1;
+  }
+  int* rec_differ = nullptr;
+  if (copies) {
+    c.Rc_one = R1; c.Erc_one = E1;
+    rec_differ = dalloc<int>(m, nullptr, {1});
+    DDMI_CHECK_HIP(hipMemsetAsync(rec_differ, 0, sizeof(int), s));
+    launch_rows_differ(cc.rec_x, 1 + m.lm, cc.rec_pos, 3, R1, c.B, rec_differ, s);
+  }
   // ---- uploads
   if (cfg.all_atoms) {
     c.atom_batch = dup(m, "atom_batch", atom_batch); c.atom_ptr = dup(m, nullptr, atom_ptr_h);
@@ -942,19 +969,20 @@ void set_complex(Model& m, const ddmi_complex& cc, hipStream_t s) {
     int HKq = 0;
     for (auto* L : all_layers) HKq = std::max(HKq, L->HKq);
     // virtual-node lists: 0 lig<-rec, 1 rec-rec, 2 lig-lig, 3 rec<-lig; all_atoms: 4 lig<-atom, 5 rec<-atom, 6 atom-atom,
-    // 7 atom<-lig, 8 atom<-rec.  (lig_v: lists of the side-stream groups, which use the second hidden-row scratch.)
-    const int ecap_v[9] = {c.Elr_cap, c.Err, c.Ell_cap, c.Elr_cap, c.Ela_cap, c.Ear, c.Eaa, c.Ela_cap, c.Ear};
-    const int gn_v[9] = {nR, nR, nL, nL, c.nA, c.nA, c.nA, nL, nR};
-    const bool lig_v[9] = {false, false, true, true, false, false, false, true, false};
-    const char* names[9] = {"vn_off_cross", "vn_off_rr", "vn_off_ll", "vn_off_rl", "vn_off_la", "vn_off_ra", "vn_off_aa",
-                            "vn_off_al", "vn_off_ar"};
+    // 7 atom<-lig, 8 atom<-rec; 9 rec-rec of graph 0 (batch of receptor copies, exec.rec_share).  (lig_v: lists of the side-stream
+    // groups, which use the second hidden-row scratch.)
+    const int ecap_v[10] = {c.Elr_cap, c.Err, c.Ell_cap, c.Elr_cap, c.Ela_cap, c.Ear, c.Eaa, c.Ela_cap, c.Ear, E1};
+    const int gn_v[10] = {nR, nR, nL, nL, c.nA, c.nA, c.nA, nL, nR, R1};
+    const bool lig_v[10] = {false, false, true, true, false, false, false, true, false, false};
+    const char* names[10] = {"vn_off_cross", "vn_off_rr", "vn_off_ll", "vn_off_rl", "vn_off_la", "vn_off_ra", "vn_off_aa",
+                             "vn_off_al", "vn_off_ar", "vn_off_rr0"};   // (vn_off_rr0 stays zero until the shared layer-0 group has run: tests)
     // Tight capacities (round 6, exec.list_caps = 1; NOT the default: neutral at 5-20 poses, -1.8 % at 40, profiles/r06_p12_*): the grids of k_conv_fused / k_vn_rows cover the CAPACITY of a list, and a workgroup whose tile does
     // not exist still has to be placed on a CU with 125-158 KB of free LDS before it can exit -- the generic bound
     // nodes + edges / 32 is twice the live count for the all-pairs cross graph (a residue's <= n_lig edges are ONE virtual node).
     // Per gather node the largest possible degree is known on the host: the other side's node count of its graph for the dynamic
     // pair graphs, the exact degree for the static relations (a crop only removes edges), neighbour cap + bonds for lig-lig.
-    long tight[9];
-    for (int i = 0; i < 9; ++i) tight[i] = -1;
+    long tight[10];
+    for (int i = 0; i < 10; ++i) tight[i] = -1;
     auto vn_of = [](long deg) { return (deg + 31) / 32; };
     auto exact = [&](const std::vector<int>& off) { long n = 0; for (size_t d = 0; d + 1 < off.size(); ++d) n += vn_of(off[d + 1] - off[d]); return n; };
     tight[0] = tight[3] = 0;
@@ -964,6 +992,7 @@ void set_complex(Model& m, const ddmi_complex& cc, hipStream_t s) {
       tight[3] += nl * vn_of(nr);     // rec<-lig: gather = ligand atom
     }
     tight[1] = exact(goff);           // rec-rec (static; the per-step crop compacts it)
+    if (copies) tight[9] = exact(std::vector<int>(goff.begin(), goff.begin() + R1 + 1));   // rec-rec of graph 0
     tight[2] = 0;
     for (int d = 0; d < nL; ++d) tight[2] += vn_of((long)c.lig_cap + bg[d]);   // lig-lig: <= lig_cap radius neighbours + its bonds
     if (cfg.all_atoms) {
@@ -976,15 +1005,17 @@ void set_complex(Model& m, const ddmi_complex& cc, hipStream_t s) {
       tight[5] = exact(h_ra.goff); tight[6] = exact(h_aa.goff); tight[8] = exact(h_ar.goff);
     }
     int vmax = 0, vmax_b = 0;
-    for (int i = 0; i < (cfg.all_atoms ? 9 : 4); ++i) {
+    for (int i = 0; i < 10; ++i) {
+      if (i < 9 ? i >= (cfg.all_atoms ? 9 : 4) : !copies) continue;
       Cx::VnSet& vs = c.vn[i];
+      vs.graphs = i == 9 ? 1 : B;
       vs.vcap = gn_v[i] + ecap_v[i] / 32 + 2;   // a gather node with deg edges: ceil(deg / 32) <= deg / 32 + 1 virtual nodes
       if (m.tight_caps && tight[i] >= 0) vs.vcap = (int)std::min<long>(vs.vcap, tight[i] + 2);
       if (m.tile_per_pose) {                    // every graph padded to whole 16-node tiles
-        vs.vcap += 16 * B;
+        vs.vcap += 16 * vs.graphs;
         vs.nvn_pad = dalloc<int>(m, i == 0 ? "vn_count_cross" : nullptr, {1}, true);
       }
-      vs.cnt = dalloc<int>(m, nullptr, {gn_v[i] + 1}); vs.voff = dalloc<int>(m, names[i], {gn_v[i] + 1});
+      vs.cnt = dalloc<int>(m, nullptr, {gn_v[i] + 1}); vs.voff = dalloc<int>(m, names[i], {gn_v[i] + 1}, i == 9);
       vs.node = dalloc<int>(m, nullptr, {vs.vcap}); vs.e0 = dalloc<int>(m, nullptr, {vs.vcap});
       const int shd = (cfg.sh_lmax + 1) * (cfg.sh_lmax + 1);
       vs.ne = dalloc<int>(m, i == 0 ? "vn_ne_cross" : nullptr, {round_up(vs.vcap, 16)});   // (named: bench.py counts the message rows a pre-reducing launch writes)
@@ -1013,6 +1044,11 @@ void set_complex(Model& m, const ddmi_complex& cc, hipStream_t s) {
                                    {c.rr_toff, c.msg[2], nL, nR}, {c.offs_r, c.msg[3], nL, nR}};
     rg[1].live = c.prered ? c.vn[0].live : nullptr;   // (copied into every list that holds the lig<-rec group)
     c.rg_all = m.cpool.upload(rg);
+    if (copies) {   // layer 0 under rec_share: the rec-rec rows of graph 0 serve every graph
+      std::vector<ReduceGroup> rs = rg;
+      rs[2].tmod = R1;
+      c.rg_all_share = m.cpool.upload(rs);
+    }
     std::vector<ReduceGroup> rl(rg.begin(), rg.begin() + 2);
     c.rg_lig = m.cpool.upload(rl);
     std::vector<ReduceGroup> r0(rg.begin(), rg.begin() + 1);
@@ -1169,6 +1205,11 @@ void set_complex(Model& m, const ddmi_complex& cc, hipStream_t s) {
       DDMI_CHECK_HIP(hipMemcpyAsync(c.rec_node_base, xin, (size_t)nR * XS * 4, hipMemcpyDeviceToDevice, s));
   }
   DDMI_CHECK_HIP(hipStreamSynchronize(s));
+  if (rec_differ) {   // (the stream has just drained: no extra wait)
+    int differ = 1;
+    DDMI_CHECK_HIP(hipMemcpy(&differ, rec_differ, sizeof(int), hipMemcpyDeviceToHost));
+    c.rec_copies = differ == 0;
+  }
   m.has_complex = true;
 }
 
@@ -1563,10 +1604,18 @@ void forward(Model& m, const float* lig_pos, const float* t_tr, const float* t_r
       }
       if (gb.n) launch_gemm_batch(gb, s);
     }
+    // Receptor copies under one t (exec.rec_share, ddmi_sample): the first layer's rec-rec group reads receptor rows, edge attributes
+    // and the sigma term only -- the same for every graph of the batch -- so it runs on graph 0 (its own list, built once per complex)
+    // and the node update reads graph 0's message rows for every graph, in the same order (bit-identical).  Layers >= 1 read
+    // pose-dependent receptor rows.  The optional layer routes keep the full group.
+    const bool rec_share = m.rec_share == 0 && m.uniform_t && c.rec_copies && !crop && !overlapped && !nu && m.grouped != 2 && Lc >= 2;
+    RunGroup g_rr0 = g_rr;
+    g_rr0.gcount = g_rr0.tcount = c.Rc_one; g_rr0.ea_rows = c.Erc_one; g_rr0.vn = 9; g_rr0.static_topo = true;
     if (overlapped) run_conv_layers_overlapped(m, g_ll, g_lr, g_rr, g_rl, crop ? c.rg_all_crop : c.rg_all, xi, s);
     else
     for (int l = 0; l < Lc; ++l, ++xi) {
-      RunGroup rr = g_rr;
+      const bool share = rec_share && l == 0;
+      RunGroup rr = share ? g_rr0 : g_rr;
       if (nu && l < Lc - 1) rr.rb_ready = c.rb_l[l];
       const std::vector<RunGroup> full = {g_ll, g_lr, rr, g_rl}, ligs = {g_ll, g_lr};
       std::vector<RunGroup> next;
@@ -1576,7 +1625,8 @@ void forward(Model& m, const float* lig_pos, const float* t_tr, const float* t_r
       const int pq = !nu ? 0 : l == 0 ? 1 : 2;
       const ConvW* Ln = next.empty() ? nullptr : &m.conv_layers[l + 1];
       if (l < Lc - 1)
-        run_conv(m, m.conv_layers[l], full, crop ? c.rg_all_crop : c.rg_all, 4, c.X[xi], c.X[xi + 1], 0, c.N, s, pq, Ln, Ln ? &next : nullptr);
+        run_conv(m, m.conv_layers[l], full, share ? c.rg_all_share : crop ? c.rg_all_crop : c.rg_all, 4, c.X[xi], c.X[xi + 1], 0, c.N, s, pq, Ln,
+                 Ln ? &next : nullptr);
       else run_conv(m, m.conv_layers[l], ligs, c.rg_lig, 2, c.X[xi], c.X[xi + 1], 0, cfg.sidechain_pred ? c.N : nL, s, pq);
       // (sidechain_pred reads the RECEPTOR rows of the last table: in the reference the last layer writes them too -- no message
       // reaches them, so they are BatchNorm(0) + the padded input row, cg_model.py:345-349 -- the score read-outs only need the ligand rows)
@@ -1742,7 +1792,14 @@ void sample(Model& m, float* lig_pos, const ddmi_sample_cfg& sc, hipStream_t s) 
     // of a forward is the same in every step -- and replayed per step.  A dependent-kernel boundary costs the same inside a graph
     // as between eager launches on this stack, and the replay's fixed cost is not hidden: 146.3 -> 145.4 poses/s at 40 poses,
     // 102.2 -> 100.5 at 5.)
-    forward(m, lig_pos, tk, tk + B, tk + 2 * B, c.s_tr, c.s_rot, torsion ? c.s_tor : nullptr, s);
+    {
+      struct UniformT {   // every graph of the step has the same t (fill_times above): forward may share pose-invariant work
+        Model& m;
+        explicit UniformT(Model& mm) : m(mm) { m.uniform_t = true; }
+        ~UniformT() { m.uniform_t = false; }
+      } uniform_t{m};
+      forward(m, lig_pos, tk, tk + B, tk + 2 * B, c.s_tr, c.s_rot, torsion ? c.s_tor : nullptr, s);
+    }
     perturb_step(m, c.s_tr, c.s_rot, torsion ? c.s_tor : nullptr, sc, k, ids_dev, s);
 #ifdef DDMI_PROFILING   // timing-only ablation builds produce garbage scores: DDMI_FREEZE_POSE keeps the graphs fixed (never in the shipped library)
     static const bool freeze = getenv("DDMI_FREEZE_POSE") != nullptr;

@@ -353,8 +353,9 @@ __global__ __launch_bounds__(256) void k_reduce_bn(const ReduceGroup* __restrict
   int cnt = 0;
   for (int g = 0; g < n_groups; ++g) {
     const ReduceGroup G = groups[g];
-    const int sl = s - G.tbase;
+    int sl = s - G.tbase;
     if (sl < 0 || sl >= G.tcount) continue;
+    if (G.tmod > 0) sl %= G.tmod;   // batch of copies: the rows of the same node of graph 0 (same rows, same order)
     const int b = G.toff[sl], e = G.toff[sl + 1];
     cnt += e - b;
     if (G.live) {   // pre-reduced group: only the rows flagged live hold (partial) sums; wave w takes the live rows of ordinal w, w + 4, ...

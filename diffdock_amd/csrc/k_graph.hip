@@ -315,6 +315,27 @@ void launch_crop_mask(const float* lpos, const float* rpos, const int* rbatch, c
   DDMI_CHECK_HIP(hipGetLastError());
 }
 
+// set_complex: is the receptor of every graph a bitwise copy of graph 0's (features and positions)?
+__global__ void k_rows_differ(const float* __restrict__ a, int lda, const float* __restrict__ b, int ldb, int n_one, long total,
+                              int* __restrict__ differ) {
+  const int ld = lda + ldb;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long row = n_one + i / ld;   // rows of graphs 1 .. copies-1
+    const int col = (int)(i % ld);
+    const long row0 = row % n_one;
+    const unsigned* p = reinterpret_cast<const unsigned*>(col < lda ? a : b);
+    const int w = col < lda ? lda : ldb, c = col < lda ? col : col - lda;
+    if (p[row * w + c] != p[row0 * w + c]) *differ = 1;   // (every writer stores the same value)
+  }
+}
+void launch_rows_differ(const float* a, int lda, const float* b, int ldb, int n_one, int copies, int* differ, hipStream_t s) {
+  const long total = (long)n_one * (copies - 1) * (lda + ldb);
+  if (total <= 0) return;
+  const int blocks = cdiv(total, 256);
+  hipLaunchKernelGGL(k_rows_differ, dim3(blocks < 2048 ? blocks : 2048), dim3(256), 0, s, a, lda, b, ldb, n_one, total, differ);
+  DDMI_CHECK_HIP(hipGetLastError());
+}
+
 // static CSRs: gather order (goff, src = tgt - nL, dst = the gather node) and target order (toff, tlist = gather-order id)
 __global__ void k_rr_filter_count(const int* __restrict__ keep, const int* __restrict__ goff, const int* __restrict__ tgt,
                                   const int* __restrict__ toff, const int* __restrict__ tlist,

@@ -177,7 +177,9 @@ struct FusedGroupedArgs {
 static_assert(sizeof(FusedGroupedArgs) <= 3072, "kernel arguments of k_conv_grouped (4 KB limit)");
 void launch_conv_grouped(const FusedGroupedArgs& G, hipStream_t s);
 
-struct ReduceGroup { const int* toff; const float* msg; int tbase, tcount; const unsigned char* live = nullptr; };   // live: rows to read (nullptr: all)
+// live: rows to read (nullptr: all).  tmod > 0: the local target index is taken modulo tmod, so every graph of a batch of copies
+// reads the message rows of graph 0 (tmod = its node count; layer-0 rec-rec group under ddmi_exec_options.rec_share); k_reduce_bn only
+struct ReduceGroup { const int* toff; const float* msg; int tbase, tcount; const unsigned char* live = nullptr; int tmod = 0; };
 // X_out[s] = BN(mean over all groups' incoming messages) + pad(X_in[s]) for s in [nbase, nbase+ncount)
 void launch_reduce_bn(const ReduceGroup* groups_dev, int n_groups, int nbase, int ncount, int D_in, int D_out,
                       const float* bn_mean, const float* bn_scale, const float* bn_bias, int residual,
@@ -214,6 +216,9 @@ void launch_cross_count(const float* lpos, const float* rpos, const int* lbatch,
                         const int* keep, int* pairrank, int* cnt_l, int* cnt_r, hipStream_t s);
 void launch_crop_mask(const float* lpos, const float* rpos, const int* rbatch, const int* lptr, int nR, float cut2, int* keep,
                       hipStream_t s);
+// *differ = 1 if any of the rows [n_one, n_one * copies) of a (ld-wide) or b (ldb-wide) differs bitwise from the row of graph 0 at
+// the same local index (rows of graph q = [q * n_one, (q + 1) * n_one)); *differ is left untouched otherwise
+void launch_rows_differ(const float* a, int lda, const float* b, int ldb, int n_one, int copies, int* differ, hipStream_t s);
 void launch_rr_filter(const int* keep, const int* goff, const int* tgt, const int* arow, const int* toff, const int* tlist,
                       const int* gnode, int nL, int nR, int* cnt_g, int* cnt_t, int* goff2, int* toff2, int* tslot_tmp,
                       int* tgt2, int* tslot2, int* arow2, hipStream_t s);

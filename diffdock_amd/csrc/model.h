@@ -123,6 +123,8 @@ struct Model {
   bool node_update = false; // exec.node_update = 1: k_node_update -- a layer's node rows and the next layer's per-node first-Linear terms in one kernel (default: k_reduce_bn + GEMM launches)
   bool vn_merge = true;     // virtual-node lists of a layer's groups in two launches (k_vn_lists, k_vn_rows_grouped); exec.vn_build = 1: one chain per group
   bool tile_per_pose = false;   // tiles of 16 virtual nodes never span two graphs (ddmi_exec_options.tile_per_pose): bit-exact shard invariance
+  int rec_share = 0;        // ddmi_exec_options.rec_share: 0 = layer-0 rec-rec messages of a batch of receptor copies computed once (graph 0), 1 = never
+  bool uniform_t = false;   // the forward in flight has one t for every graph of the batch (set by the device step loop, sample())
   double crop_cutoff = 0.0;  // > 0: receptor cropped to this distance from the ligand in ddmi_forward (crop_beyond)
   DevicePool cpool;
   struct Cx;  // defined in complex.cpp

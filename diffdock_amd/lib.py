@@ -27,7 +27,8 @@ EDGE_PRODUCTS = {"f32": 0, "bf16x4": 1}   # ddmi_config.edge_product (include/dd
 class ExecOptions(C.Structure):   # ddmi_exec_options (include/ddmi.h): all 0 = defaults
     _fields_ = [(n, C.c_int32) for n in ("streams", "dense_rows", "shared_tiles", "packed_granules", "merged_granule", "pre_reduce",
                                          "hidden_mm", "fc1_batch", "tile_split", "tile_split_small", "hidden_grid", "tp_apply",
-                                         "debug", "tile_per_pose", "layer_overlap", "grouped", "grouped_split", "vn_build", "node_update", "tile_split_last", "tile_split_rule", "group_order", "list_caps", "time_terms")]
+                                         "debug", "tile_per_pose", "layer_overlap", "grouped", "grouped_split", "vn_build", "node_update", "tile_split_last", "tile_split_rule", "group_order", "list_caps", "time_terms",
+                                         "rec_share")]
 
 
 # Harness knobs: libddmi.so reads no environment variable; the test / bench harness selects kernel routes through these
@@ -90,6 +91,7 @@ def exec_options_from_env(base=()) -> ExecOptions:
             raise DdmiError("DDMI_GROUPED: 0 / 1 (per-group launches) or 2 (grouped)")
         x.grouped = e("DDMI_GROUPED")
     if e("DDMI_GROUPED_YS") is not None: x.grouped_split = max(0, min(8, e("DDMI_GROUPED_YS")))
+    if e("DDMI_REC_SHARE") is not None: x.rec_share = 0 if e("DDMI_REC_SHARE") != 0 else 1   # 0 = layer-0 rec-rec group never shared across copies
     return x
 
 

@@ -95,6 +95,11 @@ typedef struct ddmi_exec_options {
   int32_t time_terms;       /* 1 = k_time_terms: time embedding, its per-graph linear terms and rec_sigma's second layer in one launch
                              * (measured neutral once the cross-graph search runs beside them: profiles/r06_p18_*), 0 = k_time_embedding
                              * -> k_gemm_nt_batch -> k_gemm_nt (the default)                                                           */
+  int32_t rec_share;        /* 0 = when every graph of the batch is a copy of graph 0's receptor (features, positions, contact graph) and
+                             * the forward has one t for all graphs (the ddmi_sample step loop; not ddmi_forward, whose t stays on the
+                             * device), the first interaction layer computes the rec-rec messages of graph 0 only and the node update
+                             * reads them for every graph -- bit-identical, 1/B of that group's work.  CG model, no per-step crop,
+                             * joined layers (layer_overlap, grouped = 2 and node_update keep the full group).  1 = never              */
 } ddmi_exec_options;
 
 /* Hyper-parameters: the keyword arguments get_model passes to CGModel
