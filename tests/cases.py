@@ -2,6 +2,7 @@
 and by the `-m gpu` tests on the MI355X through the same C ABI.  `make(cfg, sd)` returns a loaded MIScoreModel, `place`
 moves a batch to the model's device."""
 import copy
+import math
 
 import numpy as np
 import pytest
@@ -522,3 +523,233 @@ def sidechain_pred_under_crop_case(make, place):
     side = place(torch.empty(int(batch["receptor"].pos.shape[0]), 10))
     with pytest.raises(DdmiError):
         _l.check(m.lib, m.lib.ddmi_sidechain_pred(m._h, side.data_ptr(), None))
+
+
+# ---- one time per graph and per noise type (ddmi_forward's t_tr[B] / t_rot[B] / t_tor[B], ddmi_sample's three schedules) ----
+# Under one shared t a quantity read for the wrong graph (time embedding, hidden-row bias W1e . sig, receptor sigma rows, dynamic
+# cross cutoff, the score heads' sigma) or for the wrong noise type gives exactly the right answer; these cases give every pose
+# its own three times, far apart and permuted differently, and compare with the float64 oracle.
+
+MIXED_T = {"tr": (0.95, 0.4, 0.05), "rot": (0.3, 0.85, 0.6), "tor": (0.55, 0.1, 0.9)}
+MIXED_T_DYN = {"tr": (0.95, 0.6, 0.05), "rot": (0.3, 0.85, 0.6), "tor": (0.55, 0.1, 0.9)}   # cutoffs 3 sigma_tr + 20: 64 / 27 / 20 A
+
+
+def _times(times, B):
+    return [list(times[k]) * (B // len(times[k])) for k in ("tr", "rot", "tor")]
+
+
+def mixed_times_tile_case(make, place, n_res, n_lig, variant, dynamic=False):
+    """Tiles that straddle the three poses of a batch (the B = 3 shapes of the tile-boundary sweep): scores and the x{l} node
+    tables element-wise against the float64 oracle.  With dynamic_max_cross each pose has its own cross cutoff; the cutoffs
+    and the cross-edge count of every pose are checked against the oracle's, and the case asserts that graph 0's cutoff would
+    have given other counts."""
+    from oracle.conformer import t_to_sigma
+    from oracle.graph_ops import radius
+    from util import elem_excess, set_times
+    B = 3
+    cfg = _ddl(num_conv_layers=4, dynamic_max_cross=dynamic, tr_sigma_max=19.0 if dynamic else 5.0, **variant)
+    sd = init_state_dict(cfg, seed=7)
+    g = make_complex(seed=100 + n_res, n_res=n_res, n_lig=n_lig, lm_dim=0)
+    from diffdock_amd.synth import make_pose_list as mpl
+    dl = mpl(g, B, tr_sigma_max=5.0, seed=n_lig, initial_noise_std_proportion=0.3)
+    if dynamic:   # the synthetic pocket fits inside 20 A: move the ligands 18 A out, so each cutoff keeps another set of pairs
+        for d in dl:
+            d["ligand"].pos = d["ligand"].pos + torch.tensor([18.0, 0.0, 0.0])
+    batch = HeteroBatch.from_data_list(dl)
+    times = MIXED_T_DYN if dynamic else MIXED_T
+    set_times(batch, *_times(times, B))
+    tr, rot, tor, _, inter = oracle_model(cfg, sd, dtype=F64)(batch, return_intermediates=True)
+    R = int(g["ligand"].edge_mask.sum())
+    what = f"{n_res}/{n_lig}/{B}/{variant}/{'dynamic' if dynamic else 'static'}"
+    if dynamic:   # the oracle's cutoffs and per-pose cross-edge counts (before the batch moves to the model's device)
+        sig_tr = t_to_sigma(cfg, batch.complex_t["tr"], batch.complex_t["rot"], batch.complex_t["tor"])[0]
+        cut = (3 * sig_tr + 20).double()
+        lig, rec = batch["ligand"], batch["receptor"]
+        lpos, rpos, lb, rb = lig.pos.double(), rec.pos.double(), lig.batch.clone(), rec.batch.clone()
+
+        def per_graph(c):
+            src = radius(rpos / c[rb].unsqueeze(1), lpos / c[lb].unsqueeze(1), 1, rb, lb, max_num_neighbors=10000)[0]
+            return torch.bincount(lb[src], minlength=B).tolist()
+        want = per_graph(cut)
+        assert sum(want) == inter["edge_counts"][1]
+        assert per_graph(cut[:1].expand(B)) != want, "graph 0's cutoff gives the same counts: the case does not bite"
+    m = make(cfg, sd)
+    out = m(place(batch))[:3]
+    assert_scores_close(out[:2 + (R > 0)], (tr, rot, tor)[:2 + (R > 0)], what=what)
+    assert int(m.debug_buffer("offs_l")[-1]) == inter["edge_counts"][1]
+    if dynamic:
+        assert torch.allclose(torch.from_numpy(m.debug_buffer("cross_cutoff")).double(), cut, rtol=1e-6), what
+        offs = m.debug_buffer("offs_l")
+        ptr = [b * n_lig for b in range(B + 1)]   # ligand atoms of pose b: rows ptr[b] .. ptr[b+1]
+        got = [int(offs[ptr[b + 1]]) - int(offs[ptr[b]]) for b in range(B)]
+        assert got == want, (what, got, want)
+    for l in range(1, cfg.num_conv_layers):   # node tables after every layer that updates all rows
+        ref = inter[f"node_attr{l}"]
+        mine = torch.from_numpy(m.debug_buffer(f"x{l}"))[:ref.shape[0], :ref.shape[1]]
+        assert rel_err(mine, ref) < 1e-4 and elem_excess(mine, ref) <= 1.0, (what, l, rel_err(mine, ref), elem_excess(mine, ref))
+
+
+# discrete score-norm tables (utils/so3.py:89-93, utils/torus.py:79-83): log-sigma rounded to the nearest bin
+SO3_LO, SO3_HI, SO3_N = math.log10(0.0005), math.log10(4.0), 2000
+TOR_LO, TOR_HI, TOR_N = math.log(3e-3), math.log(2.0), 5000
+
+
+def _ref_bin_position(cfg, t_rot, t_tor):
+    """Pre-round table positions the way the reference computes them: sigma in float32 torch, then numpy float32 logs."""
+    t_rot, t_tor = torch.as_tensor(t_rot, dtype=torch.float32), torch.as_tensor(t_tor, dtype=torch.float32)
+    eps = (cfg.rot_sigma_min ** (1 - t_rot) * cfg.rot_sigma_max ** t_rot).numpy()
+    sig = (cfg.tor_sigma_min ** (1 - t_tor) * cfg.tor_sigma_max ** t_tor).numpy()
+    so3 = (np.log10(eps) - np.log10(0.0005)) / (np.log10(4) - np.log10(0.0005)) * SO3_N
+    tor = (np.log(sig / np.pi) - np.log(3e-3)) / (np.log(2) - np.log(3e-3)) * TOR_N
+    return np.asarray(so3, dtype=np.float64), np.asarray(tor, dtype=np.float64)
+
+
+def _t_at(smin, smax, log_target, log_fn):
+    """t with log(sigma(t)) = log_target, sigma(t) = smin^(1-t) smax^t."""
+    return (log_target - log_fn(smin)) / (log_fn(smax) - log_fn(smin))
+
+
+def score_norm_times(cfg, n_bins=16, deltas=(0.02, 0.002)):
+    """Per-graph (t_rot, t_tor) whose reference table positions sit at k + 0.5 +- delta for bins k spread over the reachable
+    range, plus t = 0 and t = 1."""
+    lo_r = math.ceil((math.log10(cfg.rot_sigma_min) - SO3_LO) / (SO3_HI - SO3_LO) * SO3_N)
+    hi_r = math.floor((math.log10(cfg.rot_sigma_max) - SO3_LO) / (SO3_HI - SO3_LO) * SO3_N) - 1
+    lo_t = math.ceil((math.log(cfg.tor_sigma_min / math.pi) - TOR_LO) / (TOR_HI - TOR_LO) * TOR_N)
+    hi_t = math.floor((math.log(cfg.tor_sigma_max / math.pi) - TOR_LO) / (TOR_HI - TOR_LO) * TOR_N) - 1
+    kr = np.linspace(max(lo_r, 0), min(hi_r, SO3_N - 2), n_bins).astype(int)
+    kt = np.linspace(max(lo_t, 0), min(hi_t, TOR_N - 1), n_bins).astype(int)
+    t_rot, t_tor = [0.0, 1.0], [0.0, 1.0]
+    for d in deltas:
+        for sgn in (-1, 1):
+            for a, b in zip(kr, kt[::-1]):
+                pr = a + 0.5 + sgn * d
+                pt = b + 0.5 + sgn * d
+                t_rot.append(_t_at(cfg.rot_sigma_min, cfg.rot_sigma_max, SO3_LO + pr / SO3_N * (SO3_HI - SO3_LO), math.log10))
+                t_tor.append(_t_at(cfg.tor_sigma_min / math.pi, cfg.tor_sigma_max / math.pi,
+                                   TOR_LO + pt / TOR_N * (TOR_HI - TOR_LO), math.log))
+    return t_rot, t_tor
+
+
+def score_norm_bins_case(make, place, cfg, t_rot, t_tor, tie=1e-3):
+    """One forward of a tiny complex with one (t_tr, t_rot, t_tor) per graph.  Graphs whose reference position lies within
+    `tie` bins of a rounding boundary may take either neighbour and are reported; every other graph meets the element-wise
+    bound against the float64 oracle, and where the so3 table holds NaN the kernel's rot score is NaN too."""
+    from util import elem_excess, set_times
+    B = len(t_rot)
+    t_rot = np.clip(np.asarray(t_rot, dtype=np.float32), 0, 1)
+    t_tor = np.clip(np.asarray(t_tor, dtype=np.float32), 0, 1)
+    t_tr = np.linspace(0, 1, B, dtype=np.float32)[np.random.default_rng(0).permutation(B)]
+    sd = init_state_dict(cfg, seed=5)
+    g = make_complex(seed=61, n_res=14, n_lig=8, lm_dim=cfg.lm_embedding_dim)
+    from diffdock_amd.synth import make_pose_list as mpl
+    batch = HeteroBatch.from_data_list(mpl(g, B, tr_sigma_max=cfg.tr_sigma_max, seed=62, initial_noise_std_proportion=0.3))
+    set_times(batch, t_tr, t_rot, t_tor)
+    R = int(g["ligand"].edge_mask.sum())
+    assert R > 0
+    pos_r, pos_t = _ref_bin_position(cfg, t_rot, t_tor)
+    near_r = np.abs(pos_r - np.floor(pos_r) - 0.5) < tie
+    near_t = np.abs(pos_t - np.floor(pos_t) - 0.5) < tie
+    if near_r.any() or near_t.any():
+        print(f"score-norm bins: graphs within {tie} bin of a tie (either neighbour accepted): rot {np.flatnonzero(near_r).tolist()}"
+              f" tor {np.flatnonzero(near_t).tolist()}")
+    tr, rot, tor, _ = oracle_model(cfg, sd, dtype=F64)(batch)
+    out = [o.cpu() for o in make(cfg, sd)(place(batch))[:3]]
+    assert_scores_close(out[:1], (tr,), names=("tr",), what="score-norm bins")
+    nan_ref = torch.isnan(rot).any(1)
+    assert torch.equal(torch.isnan(out[1]).any(1), nan_ref), ("NaN rows of the so3 table", nan_ref.nonzero().flatten().tolist())
+    ok_r = ~nan_ref & ~torch.from_numpy(near_r)
+    assert elem_excess(out[1][ok_r], rot[ok_r]) <= 1.0, ("rot", elem_excess(out[1][ok_r], rot[ok_r]))
+    ok_t = ~torch.from_numpy(np.repeat(near_t, R))
+    assert elem_excess(out[2][ok_t], tor[ok_t]) <= 1.0, ("tor", elem_excess(out[2][ok_t], tor[ok_t]))
+    return nan_ref
+
+
+def crop_under_three_schedules_case(make, place, cfg=TINY):
+    """A 3-step ddmi_sample with crop_beyond and three different schedules: the receptor mask the last step leaves in
+    crop_keep is the oracle's crop at that step's 3 sigma_tr + crop_beyond (utils/sampling.py:104-109), around the ligand
+    positions the oracle's own trajectory reached; with sigma_rot or sigma_tor another set of residues would be kept."""
+    from oracle.conformer import t_to_sigma
+    from oracle.sampling import sampling as oracle_sampling
+    from diffdock_amd.synth import make_pose_list as mpl
+    steps, B = 3, 2
+    cfg = cfg.replace(crop_beyond=5.0)
+    s = get_t_schedule(steps)
+    scheds = (s, s ** 3, s ** 0.25)     # last step: t = 1/3, 0.037, 0.76 -> 3 sigma = 1.1, 0.1, 3.1 A
+    sd = init_state_dict(cfg, seed=9)
+    g = make_complex(seed=71, n_res=60, n_lig=10)
+    dl = mpl(g, B, tr_sigma_max=cfg.tr_sigma_max, seed=72, initial_noise_std_proportion=0.3)
+    R = int(g["ligand"].edge_mask.sum())
+    gen = torch.Generator().manual_seed(3)
+    noise = (torch.randn(steps, B, 3, generator=gen), torch.randn(steps, B, 3, generator=gen), torch.randn(steps, B * R, generator=gen))
+    record = []
+    oracle_sampling([d.clone() for d in dl], oracle_model(cfg, sd), steps, cfg, noise, scheds, batch_size=B,
+                    no_final_step_noise=True, record=record)
+    last = [r for r in record if r["t_idx"] == steps - 1][0]
+    lig = last["pos_in"].double().reshape(B, -1, 3)
+    rec = torch.stack([d["receptor"].pos for d in dl]).double()
+    dmin = torch.cdist(rec, lig).min(-1).values.reshape(-1)     # [B * n_res]: each residue's distance to its pose's ligand
+    sig = [float(x) for x in t_to_sigma(cfg, *(float(sc[steps - 1]) for sc in scheds))]
+    cut = [3 * x + cfg.crop_beyond for x in sig]
+    want = dmin < cut[0]
+    assert not torch.equal(want, dmin < cut[1]) or not torch.equal(want, dmin < cut[2]), "sigma_rot / sigma_tor crop the same"
+    m = make(cfg, sd)
+    m.sample_batch(place(HeteroBatch.from_data_list(dl)), steps, scheds, noise=noise, no_final_step_noise=True,
+                   crop_beyond=cfg.crop_beyond)
+    keep = torch.from_numpy(np.asarray(m.debug_buffer("crop_keep"))).reshape(-1).bool()
+    assert keep.shape == want.shape and 0 < int(want.sum()) < want.numel()
+    firm = (dmin - cut[0]).abs() > 1e-2    # the two trajectories agree to ~1e-3 A; a residue on the cutoff may go either way
+    assert torch.equal(keep[firm], want[firm]), (keep.nonzero().flatten().tolist(), want.nonzero().flatten().tolist())
+    assert int(firm.sum()) >= want.numel() - 2
+
+
+def all_atom_mixed_times_case(make, place):
+    """AAModel at the DDL-synth widths with one time per graph and noise type (the 'atom' nodes carry node_t too)."""
+    from diffdock_amd.synth import make_pose_list as mpl
+    from util import elem_excess, set_times
+    from diffdock_amd.config import DDL_SYNTH
+    cfg = DDL_SYNTH.replace(all_atoms=True, num_conv_layers=4, lm_embedding_type=None)
+    sd = init_state_dict(cfg, seed=77)
+    g = make_complex(seed=12, n_res=60, n_lig=20, lm_dim=0, all_atoms=True)
+    batch = HeteroBatch.from_data_list(mpl(g, 3, tr_sigma_max=cfg.tr_sigma_max, seed=13, initial_noise_std_proportion=0.05))
+    set_times(batch, *_times(MIXED_T, 3))
+    tr, rot, tor, _, inter = oracle_model(cfg, sd, dtype=F64)(batch, return_intermediates=True)
+    m = make(cfg, sd)
+    out = m(place(batch))[:3]
+    assert inter["edge_counts"][2] > 0 and int(m.debug_buffer("offs_la_l")[-1]) == inter["edge_counts"][2]
+    assert_scores_close(out, (tr, rot, tor), what="all-atom, per-graph times")
+    for l in range(cfg.num_conv_layers - 1):   # all node rows: ligand, residues, atoms
+        ref = inter[f"node_attr{l + 1}"]
+        mine = torch.from_numpy(m.debug_buffer(f"x{l + 1}"))[:, :ref.shape[1]]
+        assert rel_err(mine, ref) < 1e-4 and elem_excess(mine, ref) <= 1.0, (l, rel_err(mine, ref), elem_excess(mine, ref))
+
+
+def clip_end_config():
+    """sigma ranges that run past both ends of both tables (so3: log10 eps below log10 5e-4 and above log10 4; torus: sigma / pi
+    below 3e-3 and above 2), with graphs in the NaN bins of the shipped so3 table (153-170, 261) and at t = 0 / 1."""
+    cfg = TINY.replace(rot_sigma_min=1e-4, rot_sigma_max=6.0, tor_sigma_min=0.005, tor_sigma_max=8.0)
+    t_rot, t_tor = score_norm_times(cfg, n_bins=12)
+    for k in (153, 160, 170, 261):
+        t_rot.append(_t_at(cfg.rot_sigma_min, cfg.rot_sigma_max, SO3_LO + k / SO3_N * (SO3_HI - SO3_LO), math.log10))
+        t_tor.append(0.5)
+    t_rot += [0.01, 0.99]
+    t_tor += [0.99, 0.01]
+    return cfg, t_rot, t_tor
+
+
+def three_schedules_loops_case(make, place, device):
+    """The reference trajectory of tiny_l1_mixt (tr, rot and tor schedules differ) through ddmi_sample's own step
+    coefficients and through the host step_coefficients loop."""
+    from diffdock_amd.sampling import sampling
+    from util import fixture_case, fixture_schedules, split_draws
+    fx, cfg, data_list = fixture_case("tiny_l1_mixt")
+    s = fx["sampling"]
+    B, R = len(data_list), int(data_list[0]["ligand"].edge_mask.sum())
+    noise = split_draws(s["draws"], s["steps"], B, R)
+    tr_s, rot_s, tor_s = fixture_schedules(s)
+    assert not np.array_equal(tr_s, rot_s) and not np.array_equal(tr_s, tor_s) and not np.array_equal(rot_s, tor_s)
+    for native in (True, False):
+        m = make(cfg, fx["state_dict"])
+        out, _ = sampling([d.clone() for d in data_list], m, s["steps"], tr_s, rot_s, tor_s, device, None, cfg, batch_size=8,
+                          noise=noise, no_final_step_noise=True, native_loop=native, **s["temp"])
+        final = torch.stack([d["ligand"].pos.cpu() for d in out])
+        assert (final - s["final_pos"]).abs().max() < 2e-3, native

@@ -94,6 +94,15 @@ def build_case(cfg, n_res, n_lig, n_samples, seed, t):
     return g, data_list, sd
 
 
+def set_times_per_graph(batch, times, all_atoms):
+    """utils/diffusion_utils.py:146-168 with one time per graph and noise type: complex_t[k] = times[k] ([B]) and
+    node_t[k] = complex_t[k][node batch] for every node type."""
+    ct = {k: torch.tensor(times[k], dtype=torch.float32) for k in ("tr", "rot", "tor")}
+    for nt in ("ligand", "receptor") + (("atom",) if all_atoms else ()):
+        batch[nt].node_t = {k: v[batch[nt].batch] for k, v in ct.items()}
+    batch.complex_t = ct
+
+
 def graph_to_dict(g):
     extra = {}
     if "atom" in g.node_types:   # all-atom graphs
@@ -196,6 +205,16 @@ def main():
                                    n_samples=2, seed=28, t=0.5)
     cases["tiny_depthwise_l2"] = dict(cfg=TINY.replace(depthwise_convolution=True, sh_lmax=2, num_conv_layers=4), n_res=20, n_lig=9,
                                       n_samples=2, seed=29, t=0.4)
+    # per-graph, per-noise-type times (complex_t[k][b], node_t[k] = complex_t[k][node batch]): B = 3 poses, all three times
+    # different in every pose, so a time-dependent quantity read for the wrong graph or the wrong noise type changes the output.
+    # The trajectory of each case runs three different decreasing schedules: tr linear, rot = tr ** 1.5, tor = sqrt(tr).
+    mixt = {"tr": [0.95, 0.4, 0.05], "rot": [0.3, 0.85, 0.6], "tor": [0.55, 0.1, 0.9]}
+    cases["tiny_l1_mixt"] = dict(cfg=TINY, n_res=40, n_lig=12, n_samples=3, seed=40, t=mixt)   # dynamic_max_cross: per-graph cutoff
+    cases["tiny_l2_mixt"] = dict(cfg=TINY.replace(sh_lmax=2, tr_sigma_max=19.0), n_res=36, n_lig=14, n_samples=3, seed=41, t=mixt)
+    cases["tiny_aa_l1_mixt"] = dict(cfg=TINY.replace(all_atoms=True, num_conv_layers=3, lig_max_radius=10.0, tr_sigma_max=2.0),
+                                    n_res=24, n_lig=10, n_samples=3, seed=42, t=mixt)
+    cases["tiny_oldscore_mixt"] = dict(cfg=TINY.replace(old=True, confidence_mode=False, sh_lmax=2, num_conv_layers=3), n_res=26,
+                                       n_lig=10, n_samples=3, seed=43, t=mixt)   # legacy class: reads rec.node_t['tr']
     if len(sys.argv) > 1:
         cases = {k: v for k, v in cases.items() if k in sys.argv[1:]}
     for name, c in cases.items():
@@ -216,7 +235,10 @@ def main():
         # ---- single forward at time t, with per-layer node tables via hooks
         batch = HeteroBatch.from_data_list(copy.deepcopy(data_list))
         B = batch.num_graphs
-        set_time(batch, None, c["t"], c["t"], c["t"], B, cfg.all_atoms, torch.device("cpu"))
+        if isinstance(c["t"], dict):
+            set_times_per_graph(batch, c["t"], cfg.all_atoms)
+        else:
+            set_time(batch, None, c["t"], c["t"], c["t"], B, cfg.all_atoms, torch.device("cpu"))
         layer_out = []
         hooks = [l.register_forward_hook(lambda m, i, o: layer_out.append(o.detach().clone()))
                  for l in (model.conv_layers if not cfg.old else [])]
@@ -252,16 +274,20 @@ def main():
         torch.manual_seed(7)
         ref_sampling.torch.normal = rec_normal
         sched = get_t_schedule("expbeta", steps)
+        scheds = (sched, sched ** 1.5, np.sqrt(sched)) if isinstance(c["t"], dict) else (sched, sched, sched)
         dl = copy.deepcopy(data_list)
         temp = dict(temp_sampling=[1.17, 2.06, 7.04], temp_psi=[0.73, 0.90, 0.59], temp_sigma_data=[0.93, 0.75, 0.69]) \
             if name == "tiny_l1" else {}
         try:
-            out_list, _ = ref_sampling.sampling(dl, model, steps, sched, sched, sched, torch.device("cpu"), t_to_sigma, args,
+            out_list, _ = ref_sampling.sampling(dl, model, steps, *scheds, torch.device("cpu"), t_to_sigma, args,
                                                 batch_size=B, no_final_step_noise=True, **temp)
         finally:
             ref_sampling.torch.normal = real_normal
         fixture["sampling"] = {"steps": steps, "temp": temp, "draws": draws,
                                "final_pos": torch.stack([d["ligand"].pos for d in out_list])}
+        if isinstance(c["t"], dict):
+            fixture["sampling"]["schedules"] = {k: torch.from_numpy(np.asarray(v, dtype=np.float64)).clone()
+                                                for k, v in zip(("tr", "rot", "tor"), scheds)}
         torch.save(fixture, os.path.join(HERE, f"{name}.pt"))
         print(name, "tr", tr[0].tolist(), "tor", tor[:3].tolist(), "n_draws", len(draws))
 

@@ -15,7 +15,7 @@ from oracle.cg_model import CGModelOracle
 from oracle.conformer import get_t_schedule
 
 import cases
-from util import assert_scores_close, fixture_case, graph_from_dict, load_fixture, oracle_model, rel_err, split_draws, tables
+from util import assert_scores_close, fixture_case, graph_from_dict, load_fixture, oracle_model, rel_err, split_draws, tables, fixture_schedules, set_fixture_time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EMU = os.path.join(ROOT, "tests", "hipemu", "libddmi_emu.so")
@@ -25,7 +25,8 @@ CASES = ["tiny_l1", "tiny_l2", "tiny_l1_1group_emb", "tiny_l2_fixedcenter", "tin
          "tiny_aa_emb_nolig",                      # AAModel: embedding layers without embed_also_ligand (zero-padded ligand rows)
          "tiny_oddpar", "tiny_aa_oddpar", "tiny_nobn_noscale",   # odd_parity (CG + all-atom); batch_norm off + scale_by_sigma off
          "tiny_sidechain",                                        # sidechain_pred: o3.Linear on the receptor rows, 4th tuple element
-         "tiny_depthwise", "tiny_depthwise_l2"]                   # depthwise_convolution: 'uvu' TensorProduct + linear_2 (sh_lmax 1 and 2)
+         "tiny_depthwise", "tiny_depthwise_l2",                   # depthwise_convolution: 'uvu' TensorProduct + linear_2 (sh_lmax 1 and 2)
+         "tiny_l1_mixt", "tiny_l2_mixt", "tiny_aa_l1_mixt"]       # one time per graph and noise type, three different schedules
 
 
 @pytest.fixture(scope="session")
@@ -55,7 +56,7 @@ def test_forward_matches_reference_fixture(name, emu_lib):
     fx, cfg, data_list = fixture_case(name)
     m = make_model(cfg, fx["state_dict"], emu_lib)
     batch = HeteroBatch.from_data_list(data_list)
-    set_time(batch, fx["t"], fx["t"], fx["t"], batch.num_graphs)
+    set_fixture_time(batch, fx["t"])
     tr, rot, tor, side = m(batch)
     ref = fx["forward"]
     if cfg.sidechain_pred:   # 4th tuple element (models/cg_model.py:397-402): [n_rec, 10]
@@ -78,15 +79,16 @@ def test_forward_matches_reference_fixture(name, emu_lib):
 
 
 @pytest.mark.parametrize("name", ["tiny_l1", "tiny_l2", "tiny_l2_crop", "tiny_aa_l1", "tiny_aa_l2", "tiny_aa_l2_emb", "tiny_2nd", "tiny_aa_2nd", "tiny_fourier",
-                                  "tiny_tpw3", "tiny_aa_emb_nolig", "tiny_oddpar", "tiny_aa_oddpar", "tiny_nobn_noscale"])
+                                  "tiny_tpw3", "tiny_aa_emb_nolig", "tiny_oddpar", "tiny_aa_oddpar", "tiny_nobn_noscale",
+                                  "tiny_l1_mixt", "tiny_l2_mixt", "tiny_aa_l1_mixt"])
 def test_device_loop_matches_reference_trajectory(name, emu_lib):
     fx, cfg, data_list = fixture_case(name)
     m = make_model(cfg, fx["state_dict"], emu_lib)
     s = fx["sampling"]
     B, R = len(data_list), int(data_list[0]["ligand"].edge_mask.sum())
     noise = split_draws(s["draws"], s["steps"], B, R)
-    sched = get_t_schedule(s["steps"])
-    pos = m.sample_batch(HeteroBatch.from_data_list(data_list), s["steps"], (sched, sched, sched), noise=noise,
+    scheds = fixture_schedules(s)
+    pos = m.sample_batch(HeteroBatch.from_data_list(data_list), s["steps"], scheds, noise=noise,
                          no_final_step_noise=True, crop_beyond=cfg.crop_beyond, **s["temp"])
     assert (pos.reshape(B, -1, 3) - s["final_pos"]).abs().max() < 2e-3   # Angstrom, 4 chaotic fp32 steps
     if cfg.crop_beyond is not None:   # the last step really cropped: fewer residues kept than present
@@ -279,7 +281,7 @@ def test_confidence_mode_matches_reference_fixture(name, emu_lib):
     m = MIScoreModel(cfg, device="cpu", lib_path=emu_lib)
     m.load_state_dict(fx["state_dict"])
     batch = HeteroBatch.from_data_list(data_list)
-    set_time(batch, fx["t"], fx["t"], fx["t"], batch.num_graphs)
+    set_fixture_time(batch, fx["t"])
     conf, atom_conf = m(batch)
     ref = fx["forward"]
     assert conf.shape == ref["confidence"].shape and rel_err(conf, ref["confidence"]) < 1e-4
@@ -296,7 +298,7 @@ def test_legacy_confidence_class_matches_reference_fixture(name, emu_lib, monkey
     interaction layer, the swapped [edge, gather, target] input of the lig->rec layer."""
     fx, cfg, data_list = fixture_case(name)
     batch = HeteroBatch.from_data_list(data_list)
-    set_time(batch, fx["t"], fx["t"], fx["t"], batch.num_graphs)
+    set_fixture_time(batch, fx["t"])
     m = MIScoreModel(cfg, device="cpu", lib_path=emu_lib)
     m.load_state_dict(fx["state_dict"])
     conf = m(batch)
@@ -304,23 +306,28 @@ def test_legacy_confidence_class_matches_reference_fixture(name, emu_lib, monkey
     assert rel_err(conf, fx["forward"]["confidence"]) < 1e-4
 
 
-def test_legacy_class_score_mode_matches_reference_fixture(emu_lib, monkeypatch):
+def test_legacy_class_score_mode_matches_reference_fixture(emu_lib, monkeypatch, name="tiny_oldscore"):
     """models/old_cg_model.py in score mode (get_model(old=True, confidence_mode=False)): 3-tuple scores and the device loop
     against the reference-executed fixture."""
-    fx, cfg, data_list = fixture_case("tiny_oldscore")
+    fx, cfg, data_list = fixture_case(name)
     s = fx["sampling"]
     B, R = len(data_list), int(data_list[0]["ligand"].edge_mask.sum())
     m = make_model(cfg, fx["state_dict"], emu_lib)
     batch = HeteroBatch.from_data_list(data_list)
-    set_time(batch, fx["t"], fx["t"], fx["t"], batch.num_graphs)
+    set_fixture_time(batch, fx["t"])
     out = m(batch)
     assert len(out) == 3
     for mine, key in zip(out, ("tr", "rot", "tor")):
         assert mine.shape == fx["forward"][key].shape and rel_err(mine, fx["forward"][key]) < 1e-4, key
-    sched = get_t_schedule(s["steps"])
-    pos = m.sample_batch(HeteroBatch.from_data_list(data_list), s["steps"], (sched, sched, sched),
+    scheds = fixture_schedules(s)
+    pos = m.sample_batch(HeteroBatch.from_data_list(data_list), s["steps"], scheds,
                          noise=split_draws(s["draws"], s["steps"], B, R), no_final_step_noise=True, **s["temp"])
     assert (pos.reshape(B, -1, 3) - s["final_pos"]).abs().max() < 2e-3
+
+
+def test_legacy_class_score_mode_with_per_graph_times_matches_reference_fixture(emu_lib, monkeypatch):
+    """The legacy class reads rec.node_t['tr'] (old_cg_model.py): per-graph, per-noise-type times."""
+    test_legacy_class_score_mode_matches_reference_fixture(emu_lib, monkeypatch, name="tiny_oldscore_mixt")
 
 
 def test_sampling_calls_confidence_model(emu_lib):
@@ -543,3 +550,27 @@ def test_fused_node_update_matches_separate_launches(emu_lib):
     cases.fused_node_update_case(emu_make(emu_lib), emu_place, modes=(1, 2))
 
 
+
+
+# ---- one time per graph and per noise type (bodies in tests/cases.py, on the GPU in tests/test_gpu_times.py) ----
+
+@pytest.mark.parametrize("n_res,n_lig,variant,dynamic", [(11, 32, "l1", True), (31, 5, "l2", False), (5, 31, "ns16", False)],
+                         ids=["r11-l32-l1-dyncross", "r31-l5-l2", "r5-l31-ns16"])
+def test_straddling_tiles_with_per_graph_times(n_res, n_lig, variant, dynamic, emu_lib):
+    variants = {"l1": dict(ns=48, nv=10, sh_lmax=1), "l2": dict(ns=48, nv=10, sh_lmax=2), "ns16": dict(ns=16, nv=10, sh_lmax=1)}
+    cases.mixed_times_tile_case(emu_make(emu_lib), emu_place, n_res, n_lig, variants[variant], dynamic)
+
+
+def test_score_norm_bins_next_to_rounding_boundaries(emu_lib):
+    from diffdock_amd.config import TINY
+    t_rot, t_tor = cases.score_norm_times(TINY)
+    cases.score_norm_bins_case(emu_make(emu_lib), emu_place, TINY, t_rot, t_tor)
+
+
+def test_score_norm_bins_at_the_clip_ends_and_nan_rows(emu_lib):
+    cfg, t_rot, t_tor = cases.clip_end_config()
+    assert cases.score_norm_bins_case(emu_make(emu_lib), emu_place, cfg, t_rot, t_tor).any()
+
+
+def test_crop_under_three_schedules_matches_oracle(emu_lib):
+    cases.crop_under_three_schedules_case(emu_make(emu_lib), emu_place)

@@ -6,12 +6,12 @@ import numpy as np
 import pytest
 import torch
 
-from diffdock_amd.hetero import HeteroBatch, set_time
+from diffdock_amd.hetero import HeteroBatch
 from oracle import conformer as oc
 from oracle.cg_model import CGModelOracle
 from oracle.layers import faster_tensor_product, gaussian_smearing
 from oracle.sampling import sampling
-from util import fixture_case, load_fixture, oracle_model, rel_err, split_draws, tables, graph_from_dict
+from util import fixture_case, load_fixture, oracle_model, rel_err, split_draws, tables, graph_from_dict, fixture_schedules, set_fixture_time
 
 CASES = ["tiny_l1", "tiny_l2", "tiny_l1_1group_emb", "tiny_l2_fixedcenter", "tiny_l2_crop", "tiny_aa_l1", "tiny_aa_l2", "tiny_aa_l2_emb",
          "tiny_noaa", "tiny_2nd", "tiny_aa_2nd",   # tiny_*2nd: use_second_order_repr (2e / 2o node blocks)
@@ -19,7 +19,8 @@ CASES = ["tiny_l1", "tiny_l2", "tiny_l1_1group_emb", "tiny_l2_fixedcenter", "tin
          "tiny_aa_emb_nolig",                      # AAModel: embedding layers without embed_also_ligand (zero-padded ligand rows)
          "tiny_oddpar", "tiny_aa_oddpar", "tiny_nobn_noscale",   # odd_parity (CG + all-atom); batch_norm off + scale_by_sigma off
          "tiny_sidechain",                                        # sidechain_pred: o3.Linear on the receptor rows, 4th tuple element
-         "tiny_depthwise", "tiny_depthwise_l2"]                   # depthwise_convolution: 'uvu' TensorProduct + linear_2 (sh_lmax 1 and 2)
+         "tiny_depthwise", "tiny_depthwise_l2",                   # depthwise_convolution: 'uvu' TensorProduct + linear_2 (sh_lmax 1 and 2)
+         "tiny_l1_mixt", "tiny_l2_mixt", "tiny_aa_l1_mixt"]       # one time per graph and noise type, three different schedules
 
 
 @pytest.mark.parametrize("name", CASES)
@@ -28,7 +29,7 @@ def test_forward_matches_reference(name):
     so3_t, tor_t = tables()
     model = oracle_model(cfg, fx["state_dict"], so3_t, tor_t)
     batch = HeteroBatch.from_data_list(data_list)
-    set_time(batch, fx["t"], fx["t"], fx["t"], batch.num_graphs)
+    set_fixture_time(batch, fx["t"])
     tr, rot, tor, side, inter = model(batch, return_intermediates=True)
     ref = fx["forward"]
     if cfg.sidechain_pred:   # models/cg_model.py:397-402
@@ -49,7 +50,7 @@ def test_confidence_matches_reference(name):
     fx, cfg, data_list = fixture_case(name)
     model = oracle_model(cfg, fx["state_dict"])
     batch = HeteroBatch.from_data_list(data_list)
-    set_time(batch, fx["t"], fx["t"], fx["t"], batch.num_graphs)
+    set_fixture_time(batch, fx["t"])
     conf, atom_conf, inter = model(batch, return_intermediates=True)
     ref = fx["forward"]
     for l, ref_nodes in enumerate(ref["conv_out"]):
@@ -68,19 +69,19 @@ def test_legacy_confidence_matches_reference(name):
     OldAtomEncoder and OldTensorProductConvLayer -- the class of the released DiffDock-L confidence checkpoint."""
     fx, cfg, data_list = fixture_case(name)
     batch = HeteroBatch.from_data_list(data_list)
-    set_time(batch, fx["t"], fx["t"], fx["t"], batch.num_graphs)
+    set_fixture_time(batch, fx["t"])
     conf = oracle_model(cfg, fx["state_dict"])(batch)
     assert conf.shape == fx["forward"]["confidence"].shape and rel_err(conf, fx["forward"]["confidence"]) < 2e-5
 
 
-def test_legacy_score_mode_matches_reference():
+def test_legacy_score_mode_matches_reference(name="tiny_oldscore"):
     """get_model(..., old=True) in score mode executed by the reference: the legacy encoder / four-layer interaction blocks
     followed by the read-outs of old_cg_model.py:293-352; forward scores and the reference sampling() trajectory."""
-    fx, cfg, data_list = fixture_case("tiny_oldscore")
+    fx, cfg, data_list = fixture_case(name)
     so3_t, tor_t = tables()
     model = oracle_model(cfg, fx["state_dict"], so3_t, tor_t)
     batch = HeteroBatch.from_data_list(data_list)
-    set_time(batch, fx["t"], fx["t"], fx["t"], batch.num_graphs)
+    set_fixture_time(batch, fx["t"])
     out = model(batch)
     assert len(out) == 3
     for mine, key in zip(out, ("tr", "rot", "tor")):
@@ -88,9 +89,14 @@ def test_legacy_score_mode_matches_reference():
     s = fx["sampling"]
     B, R = len(data_list), int(data_list[0]["ligand"].edge_mask.sum())
     noise = split_draws(s["draws"], s["steps"], B, R)
-    res = sampling(data_list, model, s["steps"], cfg, noise, batch_size=B, no_final_step_noise=True, **s["temp"])
+    res = sampling(data_list, model, s["steps"], cfg, noise, fixture_schedules(s), batch_size=B, no_final_step_noise=True, **s["temp"])
     final = torch.stack([d["ligand"].pos for d in res])
     assert (final - s["final_pos"]).abs().max() < 2e-3
+
+
+def test_legacy_score_mode_with_per_graph_times_matches_reference():
+    """The legacy class reads rec.node_t['tr'] (old_cg_model.py): per-graph, per-noise-type times."""
+    test_legacy_score_mode_matches_reference(name="tiny_oldscore_mixt")
 
 
 @pytest.mark.parametrize("name", CASES)
@@ -102,7 +108,7 @@ def test_sampling_matches_reference(name):
     B = len(data_list)
     R = int(data_list[0]["ligand"].edge_mask.sum())
     noise = split_draws(s["draws"], s["steps"], B, R)
-    out = sampling(data_list, model, s["steps"], cfg, noise, batch_size=B, no_final_step_noise=True, **s["temp"])
+    out = sampling(data_list, model, s["steps"], cfg, noise, fixture_schedules(s), batch_size=B, no_final_step_noise=True, **s["temp"])
     final = torch.stack([d["ligand"].pos for d in out])
     # 4 chaotic steps in fp32: compare in Angstrom against the reference trajectory end-points
     assert (final - s["final_pos"]).abs().max() < 2e-3, (final - s["final_pos"]).abs().max()

@@ -44,12 +44,14 @@ def test_step_coefficients_match_oracle_perturbations():
     g = torch.Generator().manual_seed(0)
     sc = (torch.randn(3, 3, generator=g), torch.randn(3, 3, generator=g), torch.randn(6, generator=g))
     z = (torch.randn(3, 3, generator=g), torch.randn(3, 3, generator=g), torch.randn(6, generator=g))
-    for kw in (dict(), temp, dict(ode=True), dict(no_final_step_noise=True)):
-        for t_idx in (0, 4):
-            ref = perturbations(cfg, t_idx, 5, (s, s, s), sc, z, **kw)
-            co = step_coefficients(cfg, t_idx, 5, (s, s, s), **kw)
-            for r, (a, b), x, zz in zip(ref, co, sc, z):
-                assert torch.allclose(r.float(), np.float32(a) * x + np.float32(b) * zz, rtol=1e-5, atol=1e-7)
+    # the shared schedule, and three different decreasing ones (a coefficient built from the wrong schedule differs)
+    for scheds in ((s, s, s), (s, s ** 1.5, np.sqrt(s)), (np.sqrt(s), s, s ** 2)):
+        for kw in (dict(), temp, dict(ode=True), dict(no_final_step_noise=True)):
+            for t_idx in (0, 2, 4):
+                ref = perturbations(cfg, t_idx, 5, scheds, sc, z, **kw)
+                co = step_coefficients(cfg, t_idx, 5, scheds, **kw)
+                for r, (a, b), x, zz in zip(ref, co, sc, z):
+                    assert torch.allclose(r.float(), np.float32(a) * x + np.float32(b) * zz, rtol=1e-5, atol=1e-7)
 
 
 def test_sampling_signature_native_and_stepwise(emu_lib):
@@ -89,6 +91,19 @@ def test_sampling_with_crop_beyond_native_and_stepwise(emu_lib):
         out, _ = sampling([d.clone() for d in data_list], m, s["steps"], sched, sched, sched, "cpu", None, cfg, batch_size=8,
                           noise=noise, no_final_step_noise=True, native_loop=native)
         assert (torch.stack([d["ligand"].pos for d in out]) - s["final_pos"]).abs().max() < 2e-3
+
+
+
+def test_sampling_with_three_schedules_native_and_stepwise(emu_lib):
+    """tr, rot and tor schedules that differ (utils/sampling.py:69 takes them separately), through both loops."""
+    import cases
+
+    def make(cfg, sd):
+        m = MIScoreModel(cfg, device="cpu", lib_path=emu_lib)
+        m.load_state_dict(sd)
+        m.set_tables(*tables())
+        return m
+    cases.three_schedules_loops_case(make, lambda x: x, "cpu")
 
 
 WORKER = r"""

@@ -47,6 +47,39 @@ def fixture_case(name):
     return fx, cfg, data_list
 
 
+def set_times(batch, t_tr, t_rot, t_tor):
+    """utils/diffusion_utils.py:146-168 with one time per graph and noise type: complex_t[k] is the [B] vector given (a scalar
+    is broadcast), node_t[k] = complex_t[k][node batch] for every node type of the batch ('atom' too when present)."""
+    B = batch.num_graphs
+    dev = batch["ligand"].pos.device
+    ct = {}
+    for k, v in zip(("tr", "rot", "tor"), (t_tr, t_rot, t_tor)):
+        v = torch.as_tensor(v, dtype=torch.float32).reshape(-1).to(dev)
+        ct[k] = (v.expand(B) if v.numel() == 1 else v).clone()
+        assert ct[k].shape == (B,), (k, tuple(v.shape), B)
+    for nt in ("ligand", "receptor") + (("atom",) if "atom" in batch.node_types else ()):
+        idx = batch[nt].batch.to(dev)
+        batch[nt].node_t = {k: v[idx] for k, v in ct.items()}
+    batch.complex_t = ct
+    return batch
+
+
+def set_fixture_time(batch, t):
+    """A fixture's time: one scalar for every graph and noise type, or {"tr": [B], "rot": [B], "tor": [B]}."""
+    if isinstance(t, dict):
+        return set_times(batch, t["tr"], t["rot"], t["tor"])
+    return set_times(batch, t, t, t)
+
+
+def fixture_schedules(s):
+    """The (tr, rot, tor) schedules of a fixture trajectory: three recorded ones, or the default schedule for all three."""
+    from oracle.conformer import get_t_schedule
+    if "schedules" in s:
+        return tuple(s["schedules"][k].numpy() for k in ("tr", "rot", "tor"))
+    sched = get_t_schedule(s["steps"])
+    return sched, sched, sched
+
+
 def oracle_model(cfg, state_dict, so3_t=None, tor_t=None, dtype=torch.float32):
     """The oracle class the configuration selects (get_model's all_atoms switch, utils/utils.py:221-224)."""
     from oracle.aa_model import AAModelOracle
