@@ -156,6 +156,14 @@ int ddmi_set_complex(ddmi_model* h, const ddmi_complex* c, ddmi_stream s) {
   });
 }
 
+int ddmi_set_batch_layout(ddmi_model* h, const ddmi_batch_layout* l, ddmi_stream s) {
+  return guard([&] {
+    DDMI_REQUIRE(h && l, DDMI_ERR_ARG, "null argument");
+    DDMI_CHECK_HIP(hipSetDevice(h->m.device));
+    set_batch_layout(h->m, *l, (hipStream_t)s);
+  });
+}
+
 int ddmi_forward(ddmi_model* h, const float* lig_pos, const float* t_tr, const float* t_rot, const float* t_tor,
                  float* tr_out, float* rot_out, float* tor_out, ddmi_stream s) {
   return guard([&] {

@@ -20,6 +20,12 @@ struct Model::Cx {
   // under one t for all graphs the layer-0 rec-rec messages are the same for every graph (forward, exec.rec_share)
   bool rec_copies = false; int Rc_one = 0, Erc_one = 0;   // residues / rec-rec edges of one copy
   ReduceGroup* rg_all_share = nullptr;                    // rg_all with the rec-rec entry folded onto graph 0 (tmod = Rc_one)
+  // torsions per graph (host, from edge_mask): graph b owns [tor_ptr_h[b], tor_ptr_h[b+1]) when tor_sorted; graph-local atom indices
+  std::vector<int> tor_ptr_h, tor_lu, tor_lv; bool tor_sorted = true;
+  // ddmi_set_batch_layout: NaN-guard groups and per-graph masks of a batch of different complexes (layout = false: copies of graph 0)
+  bool layout = false; int G = 1;
+  int *grp_ptr = nullptr, *tor_ptr = nullptr, *rot_lu = nullptr, *rot_lv = nullptr; long long* mask_off = nullptr;
+  unsigned char* mask_all = nullptr;
   std::vector<int> lig_ptr_h, rec_ptr_h;
   // static
   int *lig_batch, *rec_batch, *lig_ptr, *rec_ptr, *lig_x;
@@ -812,6 +818,13 @@ void set_complex(Model& m, const ddmi_complex& cc, hipStream_t s) {
   for (int k = 0; k < c.Eb && !cfg.no_torsion; ++k)
     if (edge_mask[k]) { tor_u.push_back(bsrc[k]); tor_v.push_back(bdst[k]); tor_b.push_back(lig_batch[bsrc[k]]); }
   DDMI_REQUIRE((int)tor_u.size() == c.nT, DDMI_ERR_ARG, "n_tor does not equal edge_mask.sum()");
+  c.tor_ptr_h.assign(c.B + 1, 0);
+  for (int t = 0; t < c.nT; ++t) {
+    if (t > 0 && tor_b[t] < tor_b[t - 1]) c.tor_sorted = false;
+    c.tor_ptr_h[tor_b[t] + 1]++;
+    c.tor_lu.push_back(tor_u[t] - c.lig_ptr_h[tor_b[t]]); c.tor_lv.push_back(tor_v[t] - c.lig_ptr_h[tor_b[t]]);
+  }
+  for (int b = 0; b < c.B; ++b) c.tor_ptr_h[b + 1] += c.tor_ptr_h[b];
   c.Et = c.nT * c.tor_cap;
   std::vector<int> tor_eu(c.Et), tor_ev(c.Et);
   for (int t = 0; t < c.nT; ++t)
@@ -1674,9 +1687,45 @@ void sidechain_pred(Model& m, float* out, hipStream_t s) {
 }
 
 // ========================================================================= conformer / sampling
+void set_batch_layout(Model& m, const ddmi_batch_layout& l, hipStream_t s) {
+  DDMI_REQUIRE(l.struct_size == sizeof(ddmi_batch_layout), DDMI_ERR_ARG, "ddmi_batch_layout.struct_size does not match this library");
+  DDMI_REQUIRE(m.has_complex, DDMI_ERR_STATE, "ddmi_set_complex must precede ddmi_set_batch_layout");
+  Cx& c = *m.cx;
+  const int G = l.num_groups;
+  DDMI_REQUIRE(G >= 1 && G <= c.B && l.group_ptr, DDMI_ERR_ARG, "need 1..num_graphs groups and group_ptr");
+  DDMI_REQUIRE(l.group_ptr[0] == 0 && l.group_ptr[G] == c.B, DDMI_ERR_ARG, "group_ptr must run from 0 to num_graphs");
+  for (int g = 0; g < G; ++g) DDMI_REQUIRE(l.group_ptr[g + 1] > l.group_ptr[g], DDMI_ERR_ARG, "empty or decreasing group in group_ptr");
+  DDMI_REQUIRE(c.tor_sorted, DDMI_ERR_ARG, "the rotatable bonds (edge_mask) are not in graph order");
+  std::vector<long long> mask_off(c.B);
+  long long bytes = 0;
+  for (int b = 0; b < c.B; ++b) {
+    mask_off[b] = bytes;
+    bytes += (long long)(c.tor_ptr_h[b + 1] - c.tor_ptr_h[b]) * (c.lig_ptr_h[b + 1] - c.lig_ptr_h[b]);
+  }
+  DDMI_REQUIRE(l.mask_rotate_bytes == bytes, DDMI_ERR_ARG,
+               "mask_rotate_bytes = " + std::to_string(l.mask_rotate_bytes) + ", the graphs' [R_b, Nl_b] blocks take " + std::to_string(bytes));
+  DDMI_REQUIRE(bytes == 0 || l.mask_rotate, DDMI_ERR_ARG, "the batch has rotatable bonds: mask_rotate is required");
+  DDMI_CHECK_HIP(hipStreamSynchronize(s));   // the previous layout may still be read by enqueued steps
+  if (!c.grp_ptr) {   // per-complex parts: uploaded once, the groups and the mask are rewritten by every call
+    c.grp_ptr = dalloc<int>(m, "layout_group_ptr", {c.B + 1});
+    c.tor_ptr = dup(m, "layout_tor_ptr", c.tor_ptr_h);
+    c.rot_lu = dup(m, nullptr, c.tor_lu); c.rot_lv = dup(m, nullptr, c.tor_lv);
+    c.mask_off = dup(m, nullptr, mask_off);
+    if (bytes) c.mask_all = dalloc<unsigned char>(m, nullptr, {bytes});
+  }
+  DDMI_CHECK_HIP(hipMemcpy(c.grp_ptr, l.group_ptr, (size_t)(G + 1) * sizeof(int), hipMemcpyHostToDevice));
+  if (bytes) DDMI_CHECK_HIP(hipMemcpy(c.mask_all, l.mask_rotate, (size_t)bytes, hipMemcpyDeviceToDevice));
+  c.layout = true; c.G = G;
+}
+
 void modify_conformer(Model& m, float* lig_pos, const float* tr, const float* rot, const float* tor, hipStream_t s) {
   DDMI_REQUIRE(m.has_complex, DDMI_ERR_STATE, "ddmi_set_complex must precede ddmi_modify_conformer");
   Cx& c = *m.cx;
+  if (c.layout) {
+    launch_modify_conformer_ragged(lig_pos, c.B, c.maxNl, c.lig_ptr, c.tor_ptr, c.rot_lu, c.rot_lv, c.mask_off, c.mask_all, tr, rot,
+                                   c.nT > 0 ? tor : nullptr, s);
+    return;
+  }
   DDMI_REQUIRE(c.uniform && c.Nl_one > 0, DDMI_ERR_STATE,
                "modify_conformer needs a batch of copies of one complex (utils/diffusion_utils.py:60-64)");
   const bool torsion = tor != nullptr && c.R_one > 0;
@@ -1747,12 +1796,14 @@ static void perturb_step(Model& m, float* tr, float* rot, float* tor, const ddmi
     p.use_rng = 1;
   }
   p.seed = sc.seed; p.sample_ids = ids_dev; p.step = k;
-  launch_perturb(p, s);
+  if (c.layout) launch_perturb_grouped(p, c.G, c.grp_ptr, c.tor_ptr, c.tor_batch, s);
+  else launch_perturb(p, s);
 }
 
 static void check_sample_cfg(Model& m, const ddmi_sample_cfg& sc) {
   DDMI_REQUIRE(sc.inference_steps > 0 && sc.tr_schedule && sc.rot_schedule && sc.tor_schedule, DDMI_ERR_ARG, "bad schedule");
-  DDMI_REQUIRE(m.cx->uniform, DDMI_ERR_STATE, "the step loop needs a batch of copies of one complex");
+  DDMI_REQUIRE(m.cx->uniform || m.cx->layout, DDMI_ERR_STATE,
+               "the step loop needs a batch of copies of one complex, or ddmi_set_batch_layout for a batch of several");
 }
 
 void perturb(Model& m, float* tr, float* rot, float* tor, const ddmi_sample_cfg& sc, int k, hipStream_t s) {

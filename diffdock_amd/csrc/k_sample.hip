@@ -124,6 +124,54 @@ void launch_perturb(const PerturbArgs& a, hipStream_t s) {
   DDMI_CHECK_HIP(hipGetLastError());
 }
 
+// k_perturb per NaN-guard group (ddmi_set_batch_layout): workgroup g owns graphs [group_ptr[g], group_ptr[g+1]) and their
+// torsions; its guard reads and fixes only those rows.  With one group of copies this is k_perturb's arithmetic and order.
+__global__ __launch_bounds__(256) void k_perturb_grouped(PerturbArgs a, const int* __restrict__ group_ptr,
+                                                         const int* __restrict__ tor_ptr, const int* __restrict__ tor_batch) {
+  __shared__ float red[512];
+  __shared__ int flag;
+  const int tid = threadIdx.x;
+  const int b0 = group_ptr[blockIdx.x], b1 = group_ptr[blockIdx.x + 1];
+  const int t0 = a.tor ? tor_ptr[b0] : 0, t1 = a.tor ? tor_ptr[b1] : 0;
+  float* tr = a.tr + 3 * b0; float* rot = a.rot + 3 * b0;
+  const int nb = b1 - b0;
+  if (tid == 0) flag = 0;
+  __syncthreads();
+  for (int b = tid; b < nb; b += 256) {
+    const float m = (tr[3 * b] + tr[3 * b + 1] + tr[3 * b + 2]) / 3.f;
+    if (m != m) flag = 1;
+  }
+  __syncthreads();
+  if (flag) {
+    nan_fix(tr, 3 * nb, red, tid);
+    __syncthreads();
+    nan_fix(rot, 3 * nb, red, tid);
+    __syncthreads();
+    if (t1 > t0) nan_fix(a.tor + t0, t1 - t0, red, tid);
+    __syncthreads();
+  }
+  for (int i = 3 * b0 + tid; i < 3 * b1; i += 256) {
+    const int b = i / 3, k = i - 3 * b;
+    const long long sid = a.sample_ids ? a.sample_ids[b] : b;
+    const float zt = a.z_tr ? a.z_tr[i] : (a.use_rng ? normal_draw(a.seed, sid, a.step, k) : 0.f);
+    const float zr = a.z_rot ? a.z_rot[i] : (a.use_rng ? normal_draw(a.seed, sid, a.step, 3 + k) : 0.f);
+    a.tr[i] = mul_add_rn(a.c_tr_s, a.tr[i], a.c_tr_z, zt);
+    a.rot[i] = mul_add_rn(a.c_rot_s, a.rot[i], a.c_rot_z, zr);
+  }
+  for (int i = t0 + tid; i < t1; i += 256) {
+    const int b = tor_batch[i], k = i - tor_ptr[b];
+    const long long sid = a.sample_ids ? a.sample_ids[b] : b;
+    const float z = a.z_tor ? a.z_tor[i] : (a.use_rng ? normal_draw(a.seed, sid, a.step, 6 + k) : 0.f);
+    a.tor[i] = mul_add_rn(a.c_tor_s, a.tor[i], a.c_tor_z, z);
+  }
+}
+void launch_perturb_grouped(const PerturbArgs& a, int G, const int* group_ptr, const int* tor_ptr, const int* tor_batch,
+                            hipStream_t s) {
+  if (G <= 0) return;
+  hipLaunchKernelGGL(k_perturb_grouped, dim3(G), dim3(256), 0, s, a, group_ptr, tor_ptr, tor_batch);
+  DDMI_CHECK_HIP(hipGetLastError());
+}
+
 __global__ void k_fill_times(float* __restrict__ t, int B, float t_tr, float t_rot, float t_tor) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < B) { t[i] = t_tr; t[B + i] = t_rot; t[2 * B + i] = t_tor; }
@@ -194,31 +242,29 @@ __device__ void max_eigvec4(double* A, double* q) {
   for (int k = 0; k < 4; ++k) q[k] = V[k * 4 + best];
 }
 
-// block (64 threads) per sample
-__global__ __launch_bounds__(64) void k_modify_conformer(float* __restrict__ pos, int Nl, int R,
-                                                         const int* __restrict__ rot_u, const int* __restrict__ rot_v,
-                                                         const unsigned char* __restrict__ mask_rotate,
-                                                         const float* __restrict__ tr, const float* __restrict__ rot,
-                                                         const float* __restrict__ tor) {
-  DDMI_DYN_SMEM(float, smem);
+// one graph (64 threads): p [Nl][3] in place; tr / rot [3] and tor [R] (or nullptr) are the graph's updates, rot_u / rot_v
+// graph-local atom indices, mask_rotate its [R][Nl] block.  smem holds 6 * Nl + 16 floats.
+__device__ __forceinline__ void conformer_update(float* __restrict__ p, int Nl, int R, const int* __restrict__ rot_u,
+                                                 const int* __restrict__ rot_v, const unsigned char* __restrict__ mask_rotate,
+                                                 const float* __restrict__ tr, const float* __restrict__ rot,
+                                                 const float* __restrict__ tor, float* smem) {
   float* rigid = smem;            // [Nl][3]
   float* flex = smem + 3 * Nl;    // [Nl][3]
   float* sc = flex + 3 * Nl;      // scratch: centre(3), R(9), t(3)
-  const int b = blockIdx.x, tid = threadIdx.x;
-  float* p = pos + (size_t)b * Nl * 3;
+  const int tid = threadIdx.x;
   for (int i = tid; i < 3 * Nl; i += 64) flex[i] = p[i];
   __syncthreads();
   if (tid == 0) {
     float cx = 0.f, cy = 0.f, cz = 0.f;
     for (int a = 0; a < Nl; ++a) { cx += flex[3 * a]; cy += flex[3 * a + 1]; cz += flex[3 * a + 2]; }
     sc[0] = cx / Nl; sc[1] = cy / Nl; sc[2] = cz / Nl;
-    axis_angle_to_matrix(rot[3 * b], rot[3 * b + 1], rot[3 * b + 2], sc + 3);
+    axis_angle_to_matrix(rot[0], rot[1], rot[2], sc + 3);
   }
   __syncthreads();
   for (int a = tid; a < Nl; a += 64) {
     const float x = flex[3 * a] - sc[0], y = flex[3 * a + 1] - sc[1], z = flex[3 * a + 2] - sc[2];
     for (int k = 0; k < 3; ++k)
-      rigid[3 * a + k] = (sc[3 + 3 * k] * x + sc[4 + 3 * k] * y + sc[5 + 3 * k] * z) + tr[3 * b + k] + sc[k];
+      rigid[3 * a + k] = (sc[3 + 3 * k] * x + sc[4 + 3 * k] * y + sc[5 + 3 * k] * z) + tr[k] + sc[k];
   }
   __syncthreads();
   if (tor == nullptr || R == 0) {
@@ -233,7 +279,7 @@ __global__ __launch_bounds__(64) void k_modify_conformer(float* __restrict__ pos
     const float px = flex[3 * v], py = flex[3 * v + 1], pz = flex[3 * v + 2];
     __syncthreads();
     const float nrm = sqrtf(vx * vx + vy * vy + vz * vz);
-    const float th = tor[(size_t)b * R + idx];
+    const float th = tor[idx];
     float Rm[9];
     axis_angle_to_matrix(vx / nrm * th, vy / nrm * th, vz / nrm * th, Rm);
     for (int a = tid; a < Nl; a += 64) {
@@ -276,12 +322,46 @@ __global__ __launch_bounds__(64) void k_modify_conformer(float* __restrict__ pos
     for (int k = 0; k < 3; ++k) p[3 * a + k] = (sc[3 + 3 * k] * x + sc[4 + 3 * k] * y + sc[5 + 3 * k] * z) + sc[12 + k];
   }
 }
+// block (64 threads) per sample
+__global__ __launch_bounds__(64) void k_modify_conformer(float* __restrict__ pos, int Nl, int R,
+                                                         const int* __restrict__ rot_u, const int* __restrict__ rot_v,
+                                                         const unsigned char* __restrict__ mask_rotate,
+                                                         const float* __restrict__ tr, const float* __restrict__ rot,
+                                                         const float* __restrict__ tor) {
+  DDMI_DYN_SMEM(float, smem);
+  const int b = blockIdx.x;
+  conformer_update(pos + (size_t)b * Nl * 3, Nl, R, rot_u, rot_v, mask_rotate, tr + 3 * b, rot + 3 * b,
+                   tor ? tor + (size_t)b * R : nullptr, smem);
+}
+// block (64 threads) per graph of a batch of different complexes (ddmi_set_batch_layout)
+__global__ __launch_bounds__(64) void k_modify_conformer_ragged(float* __restrict__ pos, const int* __restrict__ lig_ptr,
+                                                                const int* __restrict__ tor_ptr, const int* __restrict__ rot_u,
+                                                                const int* __restrict__ rot_v, const long long* __restrict__ mask_off,
+                                                                const unsigned char* __restrict__ mask_rotate,
+                                                                const float* __restrict__ tr, const float* __restrict__ rot,
+                                                                const float* __restrict__ tor) {
+  DDMI_DYN_SMEM(float, smem);
+  const int b = blockIdx.x;
+  const int a0 = lig_ptr[b], t0 = tor_ptr[b];
+  const int R = tor ? tor_ptr[b + 1] - t0 : 0;
+  conformer_update(pos + (size_t)a0 * 3, lig_ptr[b + 1] - a0, R, rot_u + t0, rot_v + t0, R ? mask_rotate + mask_off[b] : nullptr,
+                   tr + 3 * b, rot + 3 * b, R ? tor + t0 : nullptr, smem);
+}
 void launch_modify_conformer(float* pos, int B, int Nl, int R, const int* rot_u, const int* rot_v,
                              const unsigned char* mask_rotate, const float* tr, const float* rot, const float* tor,
                              hipStream_t s) {
   if (B <= 0) return;
   const size_t smem = (size_t)(6 * Nl + 16) * sizeof(float);
   hipLaunchKernelGGL(k_modify_conformer, dim3(B), dim3(64), smem, s, pos, Nl, R, rot_u, rot_v, mask_rotate, tr, rot, tor);
+  DDMI_CHECK_HIP(hipGetLastError());
+}
+void launch_modify_conformer_ragged(float* pos, int B, int maxNl, const int* lig_ptr, const int* tor_ptr, const int* rot_u,
+                                    const int* rot_v, const long long* mask_off, const unsigned char* mask_rotate, const float* tr,
+                                    const float* rot, const float* tor, hipStream_t s) {
+  if (B <= 0) return;
+  const size_t smem = (size_t)(6 * maxNl + 16) * sizeof(float);
+  hipLaunchKernelGGL(k_modify_conformer_ragged, dim3(B), dim3(64), smem, s, pos, lig_ptr, tor_ptr, rot_u, rot_v, mask_off,
+                     mask_rotate, tr, rot, tor);
   DDMI_CHECK_HIP(hipGetLastError());
 }
 

@@ -333,6 +333,10 @@ struct PerturbArgs {
   int use_rng; unsigned long long seed; const long long* sample_ids; int step;
 };
 void launch_perturb(const PerturbArgs& a, hipStream_t s);
+// ddmi_set_batch_layout: one workgroup per NaN-guard group (graphs [group_ptr[g], group_ptr[g+1])); graph b's torsions are
+// [tor_ptr[b], tor_ptr[b+1]), tor_batch[i] = graph of torsion i; the noise component of torsion i is 6 + i - tor_ptr[b].  a.R unused.
+void launch_perturb_grouped(const PerturbArgs& a, int G, const int* group_ptr, const int* tor_ptr, const int* tor_batch,
+                            hipStream_t s);
 // test entry points of the noise generator (ddmi_debug_philox / ddmi_debug_normal)
 void launch_debug_philox(const unsigned* ctr, const unsigned* key, int n, unsigned* out, hipStream_t s);
 void launch_debug_normal(unsigned long long seed, long long sample0, int n_samples, int step, int n_comp, float* out, hipStream_t s);
@@ -344,5 +348,10 @@ void launch_fill_times(float* t, int B, float t_tr, float t_rot, float t_tor, hi
 void launch_modify_conformer(float* pos, int B, int Nl, int R, const int* rot_u, const int* rot_v,
                              const unsigned char* mask_rotate, const float* tr, const float* rot, const float* tor,
                              hipStream_t s);
+// graphs of different complexes: graph b = atoms [lig_ptr[b], lig_ptr[b+1]), torsions [tor_ptr[b], tor_ptr[b+1]) with graph-local
+// rot_u / rot_v, mask block at mask_off[b] ([R_b][Nl_b]); maxNl sizes the LDS.  Same per-graph arithmetic as the uniform kernel.
+void launch_modify_conformer_ragged(float* pos, int B, int maxNl, const int* lig_ptr, const int* tor_ptr, const int* rot_u,
+                                    const int* rot_v, const long long* mask_off, const unsigned char* mask_rotate, const float* tr,
+                                    const float* rot, const float* tor, hipStream_t s);
 
 }  // namespace ddmi

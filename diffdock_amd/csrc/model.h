@@ -153,6 +153,7 @@ void build_weight_spec(Model& m);
 void commit_weights(Model& m);
 // complex.cpp
 void set_complex(Model& m, const ddmi_complex& c, hipStream_t s);
+void set_batch_layout(Model& m, const ddmi_batch_layout& l, hipStream_t s);
 // score mode: tr_out / rot_out / tor_out; confidence mode (cfg.confidence_mode): conf_out [B, num_confidence_outputs] only
 void forward(Model& m, const float* lig_pos, const float* t_tr, const float* t_rot, const float* t_tor, float* tr_out,
              float* rot_out, float* tor_out, hipStream_t s, float* conf_out = nullptr, float* atom_conf_out = nullptr);

@@ -129,6 +129,11 @@ class SampleCfg(C.Structure):
                 ("use_crop", C.c_int32), ("crop_beyond", C.c_double)]
 
 
+class BatchLayout(C.Structure):   # ddmi_batch_layout (include/ddmi.h)
+    _fields_ = [("struct_size", C.c_uint32), ("num_groups", C.c_int32), ("group_ptr", C.c_void_p), ("mask_rotate", C.c_void_p),
+                ("mask_rotate_bytes", C.c_int64)]
+
+
 def make_config(cfg) -> Config:
     c = Config()
     for name, _ in Config._fields_:
@@ -165,6 +170,7 @@ _DECLS = {
     "ddmi_set_table": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),
     "ddmi_set_time_frequencies": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "ddmi_set_complex": (C.c_int, [C.c_void_p, C.POINTER(Complex), C.c_void_p]),
+    "ddmi_set_batch_layout": (C.c_int, [C.c_void_p, C.POINTER(BatchLayout), C.c_void_p]),
     "ddmi_forward": (C.c_int, [C.c_void_p] + [C.c_void_p] * 7 + [C.c_void_p]),
     "ddmi_confidence": (C.c_int, [C.c_void_p] + [C.c_void_p] * 6 + [C.c_void_p]),
     "ddmi_sidechain_pred": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -213,6 +219,20 @@ def load(path: str | None = None):
 def check(lib, code):
     if code != 0:
         raise DdmiError(f"ddmi error {code}: {lib.ddmi_last_error().decode()}")
+
+
+def set_batch_layout(lib, handle, group_sizes, mask_rotate, stream=None):
+    """ddmi_set_batch_layout: `group_sizes` = graphs per NaN-guard group, in batch order; `mask_rotate` = the uint8 device tensor of
+    every graph's [R_b, Nl_b] block, graphs in order (None when no graph has a rotatable bond).  The library copies the mask."""
+    ptr = np.zeros(len(group_sizes) + 1, dtype=np.int32)
+    ptr[1:] = np.cumsum(np.asarray(group_sizes, dtype=np.int64))
+    lay = BatchLayout()
+    lay.struct_size = C.sizeof(BatchLayout)
+    lay.num_groups = len(group_sizes)
+    lay.group_ptr = ptr.ctypes.data
+    lay.mask_rotate = None if mask_rotate is None else mask_rotate.data_ptr()
+    lay.mask_rotate_bytes = 0 if mask_rotate is None else mask_rotate.numel()
+    check(lib, lib.ddmi_set_batch_layout(handle, C.byref(lay), stream))
 
 
 def wigner_3j(lib, l1, l2, l3):

@@ -56,6 +56,14 @@ def _mask_fingerprint(mr):
     return h.hexdigest()
 
 
+def _graph_masks(mr_attr, B):
+    """The rotatable-bond mask of every graph of a collated batch (a list with one entry per graph, each a [R_b, Nl_b] array
+    or a list of one), as numpy bool arrays; None when the batch does not carry one mask per graph."""
+    if isinstance(mr_attr, (list, tuple)) and len(mr_attr) == B:
+        return [as_numpy_mask(x) for x in mr_attr]
+    return None
+
+
 class MIScoreModel:
     def __init__(self, cfg: ModelConfig, device="cuda:0", lib_path: str | None = None):
         self.cfg = cfg
@@ -67,6 +75,7 @@ class MIScoreModel:
         self._complex_key = None
         self._complex_ref = None
         self._keep = None
+        self._layout = None   # ddmi_set_batch_layout state of the current complex (see _ensure_layout)
         self._state: Dict[str, torch.Tensor] = {}
         self._tables_set = False
         self.training = False
@@ -197,7 +206,19 @@ class MIScoreModel:
         n_tor = int(lig.edge_mask.sum())
         mask_rotate = None
         mr_attr = getattr(lig, "mask_rotate", None) if hasattr(lig, "mask_rotate") else None
-        if mr_attr is not None:
+        # per graph: atoms, rotatable bonds (graph-local ends, edge order) and mask -- a batch of copies of one complex keeps the
+        # single-mask path of ddmi_set_complex; any other batch gets every graph's own mask through ddmi_set_batch_layout
+        n_l = (lig_ptr[1:] - lig_ptr[:-1]).tolist()
+        tor_ends = bond.edge_index[:, lig.edge_mask.to(bond.edge_index.device).bool()].to("cpu")
+        tor_graph = lig.batch.to("cpu")[tor_ends[0]]
+        tor_local = [(tor_ends[:, tor_graph == b] - int(lig_ptr[b])) for b in range(B)]
+        masks = _graph_masks(mr_attr, B)
+        if masks is not None and not all(m.shape == (t.shape[1], n) or (t.shape[1] == 0 and m.size == 0)
+                                         for m, t, n in zip(masks, tor_local, n_l)):
+            masks = None
+        copies = all(n == n_l[0] and torch.equal(t, tor_local[0]) for n, t in zip(n_l, tor_local)) and \
+            (masks is None or all(np.array_equal(m, masks[0]) for m in masks))
+        if mr_attr is not None and copies:
             mr = as_numpy_mask(mr_attr)
             if mr.size and mr.shape[0] * B == n_tor and mr.shape[1] * B == lig.pos.shape[0]:
                 mask_rotate = torch.from_numpy(np.ascontiguousarray(mr.astype(np.uint8))).to(dev)
@@ -218,9 +239,32 @@ class MIScoreModel:
             names += ["atom_ptr", "atom_x", "atom_pos", "atom_edge_index", "atom_rec_edge_index"]
         for name in names:
             setattr(c, name, keep[name].data_ptr() if keep[name] is not None else None)
+        self._complex_key = self._layout = None
         _lib.check(self.lib, self.lib.ddmi_set_complex(self._h, C.byref(c), self._stream()))
         self._keep, self._complex_key, self._complex_ref = keep, key, ref
         self._B, self._n_tor, self._n_lig = B, n_tor, lig.pos.shape[0]
+        self._copies, self._graph_masks = copies, masks
+        if not copies and (masks is not None or self.cfg.no_torsion or n_tor == 0):
+            self._ensure_layout(None)
+
+    def _ensure_layout(self, groups):
+        """ddmi_set_batch_layout for the current complex when the step loop needs it: a batch that is not made of copies of one
+        complex (every graph's own mask), or NaN-guard groups other than the whole batch.  `groups` = graphs per group in batch
+        order (None = one group)."""
+        sizes = (self._B,) if groups is None else tuple(int(g) for g in groups)
+        if sum(sizes) != self._B or min(sizes) <= 0:
+            raise ValueError(f"groups {sizes} do not partition the {self._B} graphs of the batch")
+        if sizes == self._layout or (self._copies and self._layout is None and len(sizes) == 1):
+            return
+        mask = None
+        if not self.cfg.no_torsion and self._n_tor > 0:
+            if self._graph_masks is None:
+                raise _lib.DdmiError("a batch of several complexes (or several NaN-guard groups) needs the batch's per-graph "
+                                     "mask_rotate list with one [R_b, Nl_b] mask per graph")
+            blocks = [np.ascontiguousarray(m.astype(np.uint8)).reshape(-1) for m in self._graph_masks]
+            mask = torch.from_numpy(np.concatenate(blocks)).to(self.device)
+        _lib.set_batch_layout(self.lib, self._h, sizes, mask, self._stream())
+        self._layout = sizes
 
     # ------------------------------------------------------------------ model(batch)
     def __call__(self, data):
@@ -300,9 +344,11 @@ class MIScoreModel:
 
     def sample_batch(self, data, inference_steps, schedules, noise=None, seed=0, sample_ids=None, ode=False,
                      no_random=False, no_final_step_noise=False, temp_sampling=1.0, temp_psi=0.0, temp_sigma_data=0.5,
-                     crop_beyond=None):
-        """The whole step loop of sampling() (utils/sampling.py:96-191) for one collated batch, on the device."""
+                     crop_beyond=None, groups=None):
+        """The whole step loop of sampling() (utils/sampling.py:96-191) for one collated batch, on the device.  `groups` = graphs
+        per NaN-guard group in batch order (default: the whole batch is one group, as one sampling() batch)."""
         self._ensure_complex(data)
+        self._ensure_layout(groups)
         pos = data["ligand"].pos.to(self.device, torch.float32).contiguous().clone()
         sc, keep = self._sample_cfg(inference_steps, schedules, noise, seed, sample_ids, ode, no_random, no_final_step_noise,
                                     temp_sampling, temp_psi, temp_sigma_data, crop_beyond)
@@ -315,10 +361,12 @@ class MIScoreModel:
 
     def perturb(self, data, tr_score, rot_score, tor_score, t_idx, inference_steps, schedules, noise=None, seed=0,
                 sample_ids=None, ode=False, no_random=False, no_final_step_noise=False, temp_sampling=1.0, temp_psi=0.0,
-                temp_sigma_data=0.5):
+                temp_sigma_data=0.5, groups=None):
         """Scores of step t_idx -> (tr_perturb, rot_perturb, tor_perturb): NaN guard + update formulas of
-        utils/sampling.py:117-186 on the device (ddmi_perturb).  `noise` = (z_tr [steps,B,3], z_rot [steps,B,3], z_tor [steps,n_tor])."""
+        utils/sampling.py:117-186 on the device (ddmi_perturb).  `noise` = (z_tr [steps,B,3], z_rot [steps,B,3], z_tor [steps,n_tor]).
+        `groups` = graphs per NaN-guard group (the guard runs per group; default one group)."""
         self._ensure_complex(data)
+        self._ensure_layout(groups)
         dev = self.device
         f = lambda x: x.to(dev, torch.float32).contiguous().clone()
         tr, rot = f(tr_score), f(rot_score)

@@ -196,3 +196,138 @@ def sampling(data_list, model, inference_steps, tr_schedule, rot_schedule, tor_s
     if confidence is not None:
         confidence = torch.nan_to_num(torch.cat(confidence, dim=0), nan=-1000)
     return data_list, confidence
+
+
+def _pack(chunks, max_batch_graphs):
+    """Whole chunks, in order, into device batches of at most max_batch_graphs graphs (a larger chunk runs alone)."""
+    batches, cur, n = [], [], 0
+    for ch in chunks:
+        if cur and n + len(ch[2]) > max_batch_graphs:
+            batches.append(cur)
+            cur, n = [], 0
+        cur.append(ch)
+        n += len(ch[2])
+    if cur:
+        batches.append(cur)
+    return batches
+
+
+def sample_complexes(complex_data_lists, model, inference_steps, tr_schedule, rot_schedule, tor_schedule, device=None,
+                     t_to_sigma=None, model_args=None, no_random=False, ode=False, visualization_list=None, confidence_model=None,
+                     confidence_data_lists=None, confidence_model_args=None, batch_size=32, max_batch_graphs=40,
+                     no_final_step_noise=False, pivot=None, return_full_trajectory=False, temp_sampling=1.0, temp_psi=0.0,
+                     temp_sigma_data=0.5, return_features=False, seed=0, noise=None, native_loop=True):
+    """`sampling()` over several complexes at once: returns [(data_list, confidence), ...], one entry per complex.
+
+    Each complex's data_list is cut into the chunks of `batch_size` poses that sampling() would run; each chunk is one NaN-guard
+    group (utils/sampling.py:117-131 runs per sampling() batch).  Whole chunks are packed, in order, into device batches of at
+    most `max_batch_graphs` graphs, and every device batch runs one step loop (model.sample_batch, or the step-wise model(batch)
+    loop with native_loop=False).  Final poses are written back into each data_list as sampling() does, and the confidence model
+    scores each packed batch with sampling()'s per-pose crop handling.
+
+    Sample ids: pose i of complex k uses sample id offset_k + i, offset_k = the number of poses of the complexes before it, so
+    complex k gets exactly the draws of sampling(complex_data_lists[k], ..., seed=seed, sample_id_offset=offset_k).
+    `noise` = one (z_tr [steps,N_k,3], z_rot [steps,N_k,3], z_tor [steps,N_k*R_k]) per complex, laid out as sampling()'s."""
+    if visualization_list is not None or return_full_trajectory or return_features or pivot:
+        raise NotImplementedError("visualisation / trajectories / feature returns are outside the built path")
+    if max_batch_graphs < 1 or batch_size < 1:
+        raise ValueError("batch_size and max_batch_graphs must be positive")
+    lists = list(complex_data_lists)
+    if noise is not None and len(noise) != len(lists):
+        raise ValueError("noise: one (z_tr, z_rot, z_tor) per complex")
+    if confidence_data_lists is not None and len(confidence_data_lists) != len(lists):
+        raise ValueError("confidence_data_lists: one list per complex")
+    conf_crop = getattr(confidence_model_args, "crop_beyond", None) if confidence_model_args is not None else None
+    crop = getattr(model_args, "crop_beyond", None) if model_args is not None else getattr(model.cfg, "crop_beyond", None)
+    schedules = (np.asarray(tr_schedule, dtype=np.float64), np.asarray(rot_schedule, dtype=np.float64),
+                 np.asarray(tor_schedule, dtype=np.float64))
+    cfg = model.cfg if model_args is None else model_args
+    offsets = np.concatenate([[0], np.cumsum([len(dl) for dl in lists])]).astype(int).tolist()
+    chunks = [(k, lo, chunk) for k, dl in enumerate(lists) for lo, chunk in _batches(dl, batch_size)]
+    confidence = [[] for _ in lists] if confidence_model is not None else None
+    with torch.no_grad():
+        for members in _pack(chunks, max_batch_graphs):
+            graphs = [g for _, _, chunk in members for g in chunk]
+            sizes = [len(chunk) for _, _, chunk in members]
+            b = len(graphs)
+            batch = _collate(graphs)
+            if device is not None:
+                batch = batch.to(device)
+            ids = [offsets[k] + lo + i for k, lo, chunk in members for i in range(len(chunk))]
+            z = None
+            if noise is not None:
+                parts = []
+                for k, lo, chunk in members:
+                    R = int(sum(int(g["ligand"].edge_mask.sum()) for g in chunk)) // len(chunk)
+                    zk = noise[k]
+                    parts.append((zk[0][:, lo:lo + len(chunk)], zk[1][:, lo:lo + len(chunk)], zk[2][:, lo * R:(lo + len(chunk)) * R]))
+                z = tuple(torch.cat([torch.as_tensor(p[i]) for p in parts], 1) for i in range(3))
+            if native_loop and hasattr(model, "sample_batch"):
+                pos = model.sample_batch(batch, inference_steps, schedules, noise=z, seed=seed, sample_ids=ids, ode=ode,
+                                         no_random=no_random, no_final_step_noise=no_final_step_noise,
+                                         temp_sampling=temp_sampling, temp_psi=temp_psi, temp_sigma_data=temp_sigma_data,
+                                         crop_beyond=crop, groups=sizes)
+            else:   # step-wise, as sampling()'s: the NaN guard of model.perturb runs per chunk
+                pos = batch["ligand"].pos
+                try:
+                    for t_idx in range(inference_steps):
+                        set_time(batch, schedules[0][t_idx], schedules[1][t_idx], schedules[2][t_idx], b, device=pos.device)
+                        batch["ligand"].pos = pos
+                        if crop is not None:
+                            t = float(schedules[0][t_idx])
+                            model.set_crop_cutoff(cfg.tr_sigma_min ** (1 - t) * cfg.tr_sigma_max ** t * 3 + crop)
+                        tr, rot, tor = model(batch)[:3]
+                        trp, rotp, torp = model.perturb(batch, tr, rot, tor, t_idx, inference_steps, schedules, noise=z, seed=seed,
+                                                        sample_ids=ids, ode=ode, no_random=no_random,
+                                                        no_final_step_noise=no_final_step_noise, temp_sampling=temp_sampling,
+                                                        temp_psi=temp_psi, temp_sigma_data=temp_sigma_data, groups=sizes)
+                        pos = model.modify_conformer_batch(pos, batch, trp, rotp, torp)
+                finally:
+                    if crop is not None:
+                        model.set_crop_cutoff(None)
+            n_l = [int(g["ligand"].pos.shape[0]) for g in graphs]
+            pos_g = torch.split(pos, n_l)
+            j = 0
+            for k, lo, chunk in members:
+                for i in range(len(chunk)):
+                    lists[k][lo + i]["ligand"].pos = pos_g[j]
+                    j += 1
+            if confidence_model is None:
+                continue
+            if confidence_data_lists is not None:   # sampling.py:208-227 on the packed confidence graphs
+                cgraphs = [g for k, lo, chunk in members for g in confidence_data_lists[k][lo:lo + len(chunk)]]
+                alive = list(range(b))
+                if conf_crop is not None:   # every confidence graph cropped around ITS final pose; see sampling()
+                    cgraphs = [g_.clone() for g_ in cgraphs]
+                    alive = []
+                    for i, g_ in enumerate(cgraphs):
+                        g_["ligand"].pos = pos_g[i].detach().to(g_["receptor"].pos.device, g_["receptor"].pos.dtype)
+                        try:
+                            crop_beyond(g_, conf_crop, bool(getattr(confidence_model_args, "all_atoms", False)))
+                            alive.append(i)
+                        except ValueError:
+                            pass
+                    if not alive:
+                        raise ValueError(f"crop_beyond({conf_crop}) removes every residue of every pose of the batch: nothing to score")
+                cbatch = _collate([cgraphs[i] for i in alive])
+                cbatch["ligand"].pos = torch.cat([pos_g[i] for i in alive], 0).to(cbatch["ligand"].pos.device)
+                if device is not None:
+                    cbatch = cbatch.to(device)
+                set_time(cbatch, 0, 0, 0, len(alive), device=cbatch["ligand"].pos.device)
+                out = confidence_model(cbatch)
+                out = out[0] if isinstance(out, tuple) else out
+                if len(alive) != b:   # graph-level outputs back in batch order, NaN for the poses that could not be scored
+                    full = torch.full((b,) + tuple(out.shape[1:]), float("nan"), device=out.device, dtype=out.dtype)
+                    full[torch.as_tensor(alive, device=out.device)] = out
+                    out = full
+            else:   # the sampling batch itself, still carrying the last step's times
+                batch["ligand"].pos = pos
+                set_time(batch, schedules[0][-1], schedules[1][-1], schedules[2][-1], b, device=batch["ligand"].pos.device)
+                out = confidence_model(batch)
+                out = out[0] if isinstance(out, tuple) else out
+            row = 0
+            for (k, _, _), n in zip(members, sizes):
+                confidence[k].append(out[row:row + n])
+                row += n
+    return [(dl, None if confidence is None else torch.nan_to_num(torch.cat(confidence[k], dim=0), nan=-1000))
+            for k, dl in enumerate(lists)]

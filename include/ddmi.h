@@ -164,7 +164,8 @@ typedef struct ddmi_config {
  * collation produces them.  lig_ptr / rec_ptr are HOST arrays [num_graphs+1] of cumulative
  * node counts.  The conformer fields describe ONE graph and are required only by
  * ddmi_modify_conformer / ddmi_sample, which (like the reference's modify_conformer_batch,
- * utils/diffusion_utils.py:60-64) assume all graphs in the batch are copies of one complex. */
+ * utils/diffusion_utils.py:60-64) assume all graphs in the batch are copies of one complex
+ * unless ddmi_set_batch_layout gives every graph its own mask. */
 typedef struct ddmi_complex {
   int32_t num_graphs, n_lig, n_rec, n_bond_edges, n_rec_edges, n_tor;
   const int32_t* lig_ptr;        /* host [B+1] */
@@ -230,6 +231,22 @@ int ddmi_set_time_frequencies(ddmi_model* m, const float* host_freq, int64_t n);
 
 /* batch.to(device) + the receptor-side caching of CGModel.embedding (models/cg_model.py:273-295). */
 int ddmi_set_complex(ddmi_model* m, const ddmi_complex* c, ddmi_stream stream);
+
+/* Layout of a batch that packs the poses of SEVERAL complexes for the step loop (not in the reference: there every
+ * sampling() batch holds copies of one complex).  Graphs [group_ptr[g], group_ptr[g+1]) form NaN-guard group g -- one
+ * sampling() batch of the reference (utils/sampling.py:117-131 runs per batch) -- and graph b's rotatable-bond mask is its
+ * own [R_b, Nl_b] block, R_b = the rotatable bonds of graph b (edge_mask), Nl_b = its ligand atoms.  Call after
+ * ddmi_set_complex, which resets the handle to one group and graph 0's mask for every graph (a batch of copies).  With a
+ * layout set, ddmi_sample, ddmi_perturb and ddmi_modify_conformer accept batches whose graphs differ in atom and torsion
+ * counts; a graph's result does not depend on the other graphs.  The mask is copied. */
+typedef struct ddmi_batch_layout {
+  uint32_t struct_size;       /* sizeof(ddmi_batch_layout) the caller was built against                              */
+  int32_t num_groups;         /* NaN-guard groups                                                                   */
+  const int32_t* group_ptr;   /* host [num_groups+1] graph offsets, group_ptr[0] = 0, increasing, group_ptr[G] = B  */
+  const uint8_t* mask_rotate; /* device: graph b's [R_b, Nl_b] block, graphs in order; NULL if no graph has torsions */
+  int64_t mask_rotate_bytes;  /* must equal sum_b R_b * Nl_b                                                        */
+} ddmi_batch_layout;
+int ddmi_set_batch_layout(ddmi_model* m, const ddmi_batch_layout* l, ddmi_stream stream);
 
 /* tr, rot, tor = model(batch)[:3] -- models/cg_model.py:308-424.
  * lig_pos [n_lig,3]; t_* [B] = batch.complex_t[...]; outputs tr [B,3], rot [B,3], tor [n_tor]. */
