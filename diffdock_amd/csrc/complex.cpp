@@ -364,6 +364,9 @@ static void run_group(Model& m, const ConvW& L, const RunGroup& g, size_t gi, bo
   float* Hb = side ? c.Hb_b : c.Hb;
   const bool deep = L.TL > 2;   // FCBlock with hidden Linear layers: first layer as plain per-edge rows, the hidden ones as GEMMs
   const bool fuse_mm = !deep && m.fused_mm && ns % 16 == 0 && ns <= 64 && L.W1p[wg];   // first Linear inside the hidden-row kernel
+  if (m.cfg.exec.debug & 1)   // the route this group takes, for tests: hidden rows (mm / gemm / deep) and the granule loops
+    fprintf(stderr, "ddmi route %s g%d: hidden %s granules %s\n", L.name.c_str(), (int)gi,
+            fuse_mm ? "mm" : deep ? "deep" : "gemm", L.fgran_generic ? "generic" : "static");
   if (mm_all) {
     if (g.sig) rb = g.rb_ready ? g.rb_ready : rowbias;
   } else if (fuse_mm) {   // everything in the emission order of k_edge_hidden_mm (permuted copy of the first layer)

@@ -56,7 +56,8 @@ typedef struct ddmi_exec_options {
   int32_t tile_split_small; /* the same for a small group that runs next to chip-filling ones; 0 = automatic                         */
   int32_t hidden_grid;      /* workgroups of k_edge_hidden_mm; 0 = 2048                                                              */
   int32_t tp_apply;         /* read-out tensor product: 0 = by launch size, 1 = wave per pair, 2 = workgroup per edge, 3 = thread    */
-  int32_t debug;            /* 1 = print the granule list of every interaction layer to stderr at ddmi_commit_weights (tests)         */
+  int32_t debug;            /* 1 = print the granule list of every interaction layer to stderr at ddmi_commit_weights, and the route
+                             * of every edge group (hidden rows, granule loops) at each forward (tests)                            */
   int32_t tile_per_pose;    /* 1 = the 16-virtual-node tiles of k_conv_fused never span two graphs of the batch (dead virtual nodes
                              * pad every graph to whole tiles): the arithmetic of a pose then does not depend on the poses batched
                              * with it -- a sharded run is BIT-identical to the one-batch run.  0 = dense tiles.     */
