@@ -16,6 +16,48 @@ template <class F> static int guard(F&& f) {
   catch (const std::exception& e) { g_err = e.what(); return DDMI_ERR_ARG; }
 }
 
+// Execution options (include/ddmi.h, ddmi_exec_options): 0 = default everywhere; the library reads no environment variable.
+Routes ddmi::resolve_routes(const ddmi_config& cfg, int n_cus) {
+  static const struct { const char* name; int32_t ddmi_exec_options::*field; int max; } ranges[] = {
+      {"streams", &ddmi_exec_options::streams, 1}, {"dense_rows", &ddmi_exec_options::dense_rows, 2},
+      {"shared_tiles", &ddmi_exec_options::shared_tiles, 2}, {"packed_granules", &ddmi_exec_options::packed_granules, 1},
+      {"merged_granule", &ddmi_exec_options::merged_granule, 1}, {"pre_reduce", &ddmi_exec_options::pre_reduce, 1},
+      {"hidden_mm", &ddmi_exec_options::hidden_mm, 1}, {"fc1_batch", &ddmi_exec_options::fc1_batch, 1},
+      {"tile_split", &ddmi_exec_options::tile_split, 8}, {"tile_split_small", &ddmi_exec_options::tile_split_small, 8},
+      {"hidden_grid", &ddmi_exec_options::hidden_grid, 1 << 20}, {"tp_apply", &ddmi_exec_options::tp_apply, 3},
+      {"tile_per_pose", &ddmi_exec_options::tile_per_pose, 1}, {"layer_overlap", &ddmi_exec_options::layer_overlap, 2},
+      {"grouped", &ddmi_exec_options::grouped, 2}, {"grouped_split", &ddmi_exec_options::grouped_split, 8},
+      {"vn_build", &ddmi_exec_options::vn_build, 1}, {"node_update", &ddmi_exec_options::node_update, 3},
+      {"tile_split_last", &ddmi_exec_options::tile_split_last, 8}, {"tile_split_rule", &ddmi_exec_options::tile_split_rule, 2},
+      {"group_order", &ddmi_exec_options::group_order, 3}, {"list_caps", &ddmi_exec_options::list_caps, 1},
+      {"time_terms", &ddmi_exec_options::time_terms, 1}, {"rec_share", &ddmi_exec_options::rec_share, 1}};
+  const ddmi_exec_options& x = cfg.exec;
+  DDMI_REQUIRE(cfg.edge_product >= 0 && cfg.edge_product <= 1, DDMI_ERR_ARG, "ddmi_config.edge_product: 0 (f32) or 1 (bf16x4)");
+  for (auto& q : ranges)
+    DDMI_REQUIRE(x.*q.field >= 0 && x.*q.field <= q.max, DDMI_ERR_ARG, std::string("ddmi_config.exec.") + q.name + ": out of range");
+  auto use = [](int v) { return v == 0 ? Use::by_rule : v == 1 ? Use::never : Use::always; };
+  Routes r;
+  r.two_streams = x.streams == 0;
+  r.layer_overlap = x.layer_overlap;
+  r.shared_tiles = use(x.shared_tiles); r.dense_rows = use(x.dense_rows);
+  r.merged_granule = x.merged_granule == 0; r.packed_granules = x.packed_granules == 0;
+  r.tp_form = x.tp_apply - 1;
+  r.fc1_batch = x.fc1_batch == 0; r.hidden_mm = x.hidden_mm == 0; r.pre_reduce = x.pre_reduce == 0;
+  r.tile_split = x.tile_split; r.tile_split_small = x.tile_split_small; r.tile_split_last = x.tile_split_last;
+  r.round_split = x.tile_split_rule != 1; r.round_split_small = x.tile_split_rule == 2;
+  r.list_caps = x.list_caps == 1; r.time_terms = x.time_terms == 1;
+  r.group_order = x.group_order;
+  r.n_cus = n_cus;
+  if (x.hidden_grid > 0) r.hidden_grid = x.hidden_grid;
+  r.grouped = x.grouped; r.grouped_split = x.grouped_split;
+  r.node_update = x.node_update >= 1;
+  r.node_update_wpn = x.node_update == 2 ? 1 : x.node_update == 3 ? 4 : 0;
+  r.vn_merge = x.vn_build == 0;
+  r.tile_per_pose = x.tile_per_pose != 0;
+  r.rec_share = x.rec_share == 0;
+  return r;
+}
+
 extern "C" {
 
 const char* ddmi_last_error(void) { return g_err.c_str(); }
@@ -26,60 +68,19 @@ int ddmi_create(const ddmi_config* cfg, int device, ddmi_model** out) {
     DDMI_REQUIRE(cfg->struct_size == sizeof(ddmi_config), DDMI_ERR_ARG,
                  "ddmi_config.struct_size != sizeof(ddmi_config) of this library: the caller was built against another include/ddmi.h");
     DDMI_CHECK_HIP(hipSetDevice(device));
-    auto* h = new ddmi_model();
+    std::unique_ptr<ddmi_model> h(new ddmi_model());
     h->m.cfg = *cfg;
     h->m.device = device;
-    try { build_weight_spec(h->m); } catch (...) { delete h; throw; }
-    {   // execution options (include/ddmi.h, ddmi_exec_options): 0 = default everywhere; the library reads no environment variable
-      const ddmi_exec_options& x = h->m.cfg.exec;
-      auto in = [&](int v, int hi, const char* name) {
-        if (v < 0 || v > hi) { delete h; throw Error(DDMI_ERR_ARG, std::string("ddmi_config.exec.") + name + ": out of range"); }
-      };
-      if (h->m.cfg.edge_product < 0 || h->m.cfg.edge_product > 1) { delete h; throw Error(DDMI_ERR_ARG, "ddmi_config.edge_product: 0 (f32) or 1 (bf16x4)"); }
-      in(x.streams, 1, "streams"); in(x.dense_rows, 2, "dense_rows"); in(x.shared_tiles, 2, "shared_tiles");
-      in(x.packed_granules, 1, "packed_granules"); in(x.merged_granule, 1, "merged_granule"); in(x.pre_reduce, 1, "pre_reduce");
-      in(x.hidden_mm, 1, "hidden_mm"); in(x.fc1_batch, 1, "fc1_batch"); in(x.tile_split, 8, "tile_split");
-      in(x.tile_split_small, 8, "tile_split_small"); in(x.hidden_grid, 1 << 20, "hidden_grid"); in(x.tp_apply, 3, "tp_apply");
-      in(x.tile_per_pose, 1, "tile_per_pose"); in(x.layer_overlap, 2, "layer_overlap");
-      in(x.grouped, 2, "grouped"); in(x.grouped_split, 8, "grouped_split"); in(x.vn_build, 1, "vn_build"); in(x.node_update, 3, "node_update"); in(x.tile_split_last, 8, "tile_split_last"); in(x.tile_split_rule, 2, "tile_split_rule"); in(x.group_order, 3, "group_order"); in(x.list_caps, 1, "list_caps"); in(x.time_terms, 1, "time_terms");
-      in(x.rec_share, 1, "rec_share");
-      h->m.two_streams = x.streams == 0;
-      h->m.fused_dense = x.dense_rows == 0 ? 1 : x.dense_rows == 1 ? 0 : 2;
-      h->m.fused_shared = x.shared_tiles == 0 ? 1 : x.shared_tiles == 1 ? 0 : 2;
-      h->m.fused_pack = x.packed_granules == 0;
-      h->m.fused_tri = x.merged_granule == 0;
-      h->m.fused_prered = x.pre_reduce == 0;
-      h->m.fused_mm = x.hidden_mm == 0;
-      h->m.fc1_batch = x.fc1_batch == 0;
-      h->m.fused_ysplit = x.tile_split;
-      h->m.fused_ysplit_small = x.tile_split_small;
-      h->m.eh_grid = x.hidden_grid > 0 ? x.hidden_grid : 2048;
-      h->m.tp_form = x.tp_apply == 0 ? -1 : x.tp_apply - 1;   // 0 wave, 1 edge, 2 thread
-      h->m.tile_per_pose = x.tile_per_pose != 0;
-      h->m.layer_overlap = x.layer_overlap;
-      h->m.grouped = x.grouped;
-      h->m.grouped_split = x.grouped_split;
-      h->m.vn_merge = x.vn_build == 0;
-      h->m.node_update = x.node_update >= 1;
-      h->m.node_update_wpn = x.node_update == 2 ? 1 : x.node_update == 3 ? 4 : 0;
-      h->m.fused_ysplit_last = x.tile_split_last;
-      h->m.ys_rounds = x.tile_split_rule != 1;
-      h->m.ys_rounds_small = x.tile_split_rule == 2;
-      h->m.group_order = x.group_order;
-      h->m.tight_caps = x.list_caps == 1;
-      h->m.time_terms_fused = x.time_terms == 1;
-      h->m.rec_share = x.rec_share;
-      {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus >= 16) h->m.n_cus = cus;
-      }
-    }
+    build_weight_spec(h->m);
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus < 16) cus = Routes().n_cus;
+    h->m.r = resolve_routes(h->m.cfg, cus);
     DDMI_CHECK_HIP(hipStreamCreateWithFlags(&h->m.side_stream, hipStreamNonBlocking));
     DDMI_CHECK_HIP(hipEventCreate(&h->m.ev_fork));
     DDMI_CHECK_HIP(hipEventCreate(&h->m.ev_join));
     DDMI_CHECK_HIP(hipEventCreate(&h->m.ev_cross));
     DDMI_CHECK_HIP(hipEventCreate(&h->m.ev_terms));
-    *out = h;
+    *out = h.release();
   });
 }
 

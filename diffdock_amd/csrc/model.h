@@ -61,6 +61,43 @@ struct Mlp2W { float *W0 = nullptr, *b0 = nullptr, *W3 = nullptr, *b3 = nullptr;
 
 struct DebugEntry { const void* ptr; std::vector<int64_t> shape; bool is_int; };
 
+// The kernel routes a model runs: ddmi_config.exec decoded ONCE (resolve_routes).  A member that passes an option through carries the
+// option's name.  ddmi_exec_options spells every switch "0 = the default route"; here a bool has one, positive meaning -- true = the
+// route it names runs -- whatever the option's or the harness variable's polarity is.
+enum class Use { never, by_rule, always };
+struct Routes {
+  bool two_streams = true;      // ligand-gather edge groups on the side stream (exec.streams = 0)
+  int layer_overlap = 0;        // 0 joined layers (run_conv), 1 overlapped layer boundaries for chip-filling batches, 2 for every batch
+  Use shared_tiles = Use::by_rule;   // rec<-lig group contracts the distinct gather nodes of a tile on the 4x4x1 MFMA; always: every dense group (tests)
+  Use dense_rows = Use::by_rule;     // branch-free dense-row main loop; by_rule: groups with >= 20 edges per gather node
+  bool merged_granule = true;   // the three light granules of a single-chain 48-channel scalar block as one (exec.merged_granule = 0)
+  bool packed_granules = true;  // packed granules for output blocks of <= 10 channels (exec.packed_granules = 0)
+  int tp_form = -1;             // read-out tensor product: -1 by launch size; exec.tp_apply - 1 forces 0 wave, 1 edge, 2 thread (tests)
+  bool fc1_batch = true;        // per-node / per-graph terms of the first Linear of all groups of a small layer in one launch (exec.fc1_batch = 0)
+  bool hidden_mm = true;        // hidden rows straight from the edge attributes (k_edge_hidden_mm, exec.hidden_mm = 0); false: GEMMs + k_edge_hidden
+  bool pre_reduce = true;       // in-tile pre-reduction of the lig<-rec messages (exec.pre_reduce = 0); false: one message row per edge
+  int tile_split = 0;           // workgroups per 16-virtual-node tile (granule ranges); 0 = spread launches with few tiles over the CUs
+  int tile_split_small = 0;     // the same for a small group next to chip-filling ones; 0 = automatic
+  int tile_split_last = 0;      // the same for the last chip-filling launch of each stream in a layer; 0 = as the others
+  bool round_split = true;      // chip-filling groups: granule-range split from the round model (exec.tile_split_rule != 1; 1: one item per tile)
+  bool round_split_small = false;   // the round model also for the groups of small layers (exec.tile_split_rule = 2; A/B)
+  bool list_caps = false;       // virtual-node list capacities from per-node degree bounds (default: nodes + edges / 32)
+  bool time_terms = false;      // time embedding + its per-graph linear terms + rec_sigma's second layer in one launch (k_time_terms)
+  int group_order = 0;          // issue order of a layer's groups on their streams (bits: 1 = side stream reversed, 2 = main stream reversed)
+  int n_cus = 256;              // compute units of the device (hipDeviceProp_t::multiProcessorCount)
+  int hidden_grid = 2048;       // workgroups of k_edge_hidden_mm (exec.hidden_grid, 0 = 2048)
+  int grouped = 0;              // grouped dispatch of a layer's edge groups: 0 / 1 = per-group launches on two streams (default), 2 = grouped wherever supported
+  int grouped_split = 0;        // workgroups per tile in grouped launches; 0 = grouped_target / tiles of the layer
+  int grouped_target = 1536;
+  bool node_update = false;     // exec.node_update >= 1: k_node_update -- a layer's node rows and the next layer's per-node first-Linear terms in one kernel (default: k_reduce_bn + GEMM launches)
+  int node_update_wpn = 0;      // k_node_update: waves per node, 0 = by node count (exec.node_update = 2 / 3 force sixteen / four nodes per workgroup)
+  bool vn_merge = true;         // virtual-node lists of a layer's groups in two launches (exec.vn_build = 0); false: one chain per group
+  bool tile_per_pose = false;   // tiles of 16 virtual nodes never span two graphs: bit-exact shard invariance
+  bool rec_share = true;        // layer-0 rec-rec messages of a batch of receptor copies computed once, on graph 0 (exec.rec_share = 0)
+};
+// throws DDMI_ERR_ARG "ddmi_config.exec.<name>: out of range" for the first option outside its range (api.cpp)
+Routes resolve_routes(const ddmi_config& cfg, int n_cus);
+
 struct Model {
   ddmi_config cfg{};
   int device = 0;
@@ -95,39 +132,12 @@ struct Model {
   bool has_complex = false;
   hipStream_t side_stream = nullptr;   // ligand-gather edge groups run here, concurrently with the receptor-gather ones
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_cross = nullptr, ev_terms = nullptr;
-  bool two_streams = true;
-  int layer_overlap = 0;               // 0 joined layers (run_conv), 1 overlapped layer boundaries for chip-filling batches, 2 for every batch
+  Routes r;                            // the kernel routes of this model (resolve_routes, once, in ddmi_create)
   std::vector<hipEvent_t> ev_pipe;     // run_conv_layers_overlapped: [layer][group launch done / node rows written]
-  int fused_shared = 1;     // 1: rec<-lig group contracts the distinct gather nodes of a tile on the 4x4x1 MFMA; 0: per virtual node; 2: every dense group (tests)
-  bool fused_tri = true;    // the three light granules of a single-chain 48-channel scalar block as one (exec.merged_granule = 1: separate)
-  bool fused_pack = true;   // packed granules for output blocks of <= 10 channels (exec.packed_granules = 1: classic granules only)
-  int tp_form = -1;         // read-out tensor product: -1 by launch size; exec.tp_apply forces one form (tests)
-  bool fc1_batch = true;    // per-node / per-graph terms of the first Linear of all groups of a layer in one launch (exec.fc1_batch = 1: per group)
-  bool fused_mm = true;     // hidden rows straight from the edge attributes (k_edge_hidden_mm); exec.hidden_mm = 1: GEMMs + k_edge_hidden
-  int fused_dense = 1;      // branch-free dense-row main loop: 0 never, 1 groups with >= 20 edges per gather node, 2 always
-  bool fused_prered = true; // in-tile pre-reduction of the lig<-rec messages (exec.pre_reduce = 1: one message row per edge)
-  int fused_ysplit = 0;     // workgroups per 16-virtual-node tile (granule ranges); 0 = spread launches with few tiles over the CUs
-  int fused_ysplit_small = 0;   // the same for a small group next to chip-filling ones (ddmi_exec_options.tile_split_small); 0 = automatic
-  bool tight_caps = false;      // exec.list_caps = 1: virtual-node list capacities from per-node degree bounds (default: nodes + edges / 32)
-  bool time_terms_fused = false; // exec.time_terms = 1: time embedding + its per-graph linear terms + rec_sigma's second layer in one launch (k_time_terms)
-  int group_order = 0;          // issue order of a layer's groups on their streams (exec.group_order bits: 1 = side stream reversed, 2 = main stream reversed)
-  bool ys_rounds_small = false; // the round model also for the groups of small layers (exec.tile_split_rule = 2; A/B)
-  bool ys_rounds = true;        // chip-filling groups: granule-range split from the round model (exec.tile_split_rule = 1: one item per tile, rounds 2-5)
-  int n_cus = 256;              // compute units of the device (hipDeviceProp_t::multiProcessorCount)
-  int fused_ysplit_last = 0;    // the same for the last chip-filling launch of each stream in a layer (ddmi_exec_options.tile_split_last); 0 = as the others
-  int eh_grid = 2048;       // workgroups of k_edge_hidden_mm (ddmi_exec_options.hidden_grid)
-  int grouped = 0;          // grouped dispatch of a layer's edge groups (ddmi_exec_options.grouped): 0 / 1 = per-group launches on two streams (default), 2 = grouped wherever supported
-  int grouped_split = 0;    // workgroups per tile in grouped launches (exec.grouped_split); 0 = grouped_target / tiles of the layer
-  int grouped_target = 1536;
-  int node_update_wpn = 0;  // k_node_update: waves per node, 0 = by node count (exec.node_update = 2 / 3 force sixteen / four nodes per workgroup)
-  bool node_update = false; // exec.node_update = 1: k_node_update -- a layer's node rows and the next layer's per-node first-Linear terms in one kernel (default: k_reduce_bn + GEMM launches)
-  bool vn_merge = true;     // virtual-node lists of a layer's groups in two launches (k_vn_lists, k_vn_rows_grouped); exec.vn_build = 1: one chain per group
-  bool tile_per_pose = false;   // tiles of 16 virtual nodes never span two graphs (ddmi_exec_options.tile_per_pose): bit-exact shard invariance
-  int rec_share = 0;        // ddmi_exec_options.rec_share: 0 = layer-0 rec-rec messages of a batch of receptor copies computed once (graph 0), 1 = never
   bool uniform_t = false;   // the forward in flight has one t for every graph of the batch (set by the device step loop, sample())
   double crop_cutoff = 0.0;  // > 0: receptor cropped to this distance from the ligand in ddmi_forward (crop_beyond)
   DevicePool cpool;
-  struct Cx;  // defined in complex.cpp
+  struct Cx;  // cx.h
   std::shared_ptr<Cx> cx;
   std::map<std::string, DebugEntry> debug;
   // ---- kernel timing
@@ -154,11 +164,13 @@ void commit_weights(Model& m);
 // complex.cpp
 void set_complex(Model& m, const ddmi_complex& c, hipStream_t s);
 void set_batch_layout(Model& m, const ddmi_batch_layout& l, hipStream_t s);
+// forward.cpp
 // score mode: tr_out / rot_out / tor_out; confidence mode (cfg.confidence_mode): conf_out [B, num_confidence_outputs] only
 void forward(Model& m, const float* lig_pos, const float* t_tr, const float* t_rot, const float* t_tor, float* tr_out,
              float* rot_out, float* tor_out, hipStream_t s, float* conf_out = nullptr, float* atom_conf_out = nullptr);
-void modify_conformer(Model& m, float* lig_pos, const float* tr, const float* rot, const float* tor, hipStream_t s);
 void sidechain_pred(Model& m, float* out, hipStream_t s);   // model(batch)[3] of the last forward (models/cg_model.py:397-402)
+// sample.cpp
+void modify_conformer(Model& m, float* lig_pos, const float* tr, const float* rot, const float* tor, hipStream_t s);
 void sample(Model& m, float* lig_pos, const ddmi_sample_cfg& sc, hipStream_t s);
 // NaN guard + score / noise combination of step k (utils/sampling.py:117-186) on score arrays, in place
 void perturb(Model& m, float* tr, float* rot, float* tor, const ddmi_sample_cfg& sc, int k, hipStream_t s);

@@ -1,0 +1,155 @@
+// The reverse-diffusion loop on the device (reference sampling() utils/sampling.py:96-191): conformer update, score / noise
+// combination of a step, and the step loop around forward().
+#include <cmath>
+#include <cstdlib>
+#include <string>
+
+#include "cx.h"
+
+namespace ddmi {
+
+void modify_conformer(Model& m, float* lig_pos, const float* tr, const float* rot, const float* tor, hipStream_t s) {
+  DDMI_REQUIRE(m.has_complex, DDMI_ERR_STATE, "ddmi_set_complex must precede ddmi_modify_conformer");
+  Cx& c = *m.cx;
+  if (c.layout) {
+    launch_modify_conformer_ragged(lig_pos, c.B, c.maxNl, c.lig_ptr, c.tor_ptr, c.rot_lu, c.rot_lv, c.mask_off, c.mask_all, tr, rot,
+                                   c.nT > 0 ? tor : nullptr, s);
+    return;
+  }
+  DDMI_REQUIRE(c.uniform && c.Nl_one > 0, DDMI_ERR_STATE,
+               "modify_conformer needs a batch of copies of one complex (utils/diffusion_utils.py:60-64)");
+  const bool torsion = tor != nullptr && c.R_one > 0;
+  DDMI_REQUIRE(!torsion || c.mask_rotate, DDMI_ERR_STATE, "mask_rotate was not provided to ddmi_set_complex");
+  launch_modify_conformer(lig_pos, c.B, c.Nl_one, torsion ? c.R_one : 0, c.rot_u, c.rot_v, c.mask_rotate, tr, rot,
+                          torsion ? tor : nullptr, s);
+}
+
+// Sample ids of the batch (keys of the counter-based generator) on the device: staged through a pinned host buffer, so
+// the caller's array is consumed before this returns and nothing waits for the stream (the event only guards the reuse of
+// the staging buffer by a later call).
+static const long long* upload_sample_ids(Model& m, const int64_t* ids, hipStream_t s) {
+  Cx& c = *m.cx;
+  if (!ids) return nullptr;
+  if (!c.s_ids) {
+    c.s_ids = m.cpool.alloc<long long>(c.B);
+    DDMI_CHECK_HIP(hipHostMalloc(reinterpret_cast<void**>(&c.s_ids_host), (size_t)c.B * 8));
+    DDMI_CHECK_HIP(hipEventCreate(&c.s_ids_ev));
+  } else {
+    DDMI_CHECK_HIP(hipEventSynchronize(c.s_ids_ev));
+  }
+  for (int b = 0; b < c.B; ++b) c.s_ids_host[b] = ids[b];
+  DDMI_CHECK_HIP(hipMemcpyAsync(c.s_ids, c.s_ids_host, (size_t)c.B * 8, hipMemcpyHostToDevice, s));
+  DDMI_CHECK_HIP(hipEventRecord(c.s_ids_ev, s));
+  return c.s_ids;
+}
+
+// Step k of utils/sampling.py:117-186 on score arrays (in place): NaN guard, then score and noise coefficients evaluated on
+// the host in float64 exactly as the reference's 0-dim float64 tensors are.
+static void perturb_step(Model& m, float* tr, float* rot, float* tor, const ddmi_sample_cfg& sc, int k,
+                         const long long* ids_dev, hipStream_t s) {
+  Cx& c = *m.cx;
+  const ddmi_config& cfg = m.cfg;
+  const int steps = sc.inference_steps, B = c.B;
+  const bool torsion = tor != nullptr && !cfg.no_torsion && c.nT > 0;
+  const bool last = k == steps - 1;
+  const double t_tr = sc.tr_schedule[k], t_rot = sc.rot_schedule[k], t_tor = sc.tor_schedule[k];
+  const double dt_tr = last ? t_tr : t_tr - sc.tr_schedule[k + 1];
+  const double dt_rot = last ? t_rot : t_rot - sc.rot_schedule[k + 1];
+  const double dt_tor = last ? t_tor : t_tor - sc.tor_schedule[k + 1];
+  const double s_tr = std::pow((double)cfg.tr_sigma_min, 1 - t_tr) * std::pow((double)cfg.tr_sigma_max, t_tr);
+  const double s_rot = std::pow((double)cfg.rot_sigma_min, 1 - t_rot) * std::pow((double)cfg.rot_sigma_max, t_rot);
+  const double s_tor = std::pow((double)cfg.tor_sigma_min, 1 - t_tor) * std::pow((double)cfg.tor_sigma_max, t_tor);
+  const bool zero_noise = sc.no_random || (sc.no_final_step_noise && last) || sc.ode;
+  auto coeffs = [&](double sigma, double smin, double smax, double dt, int i, float& cs, float& cz) {
+    const double g = sigma * std::sqrt(2.0 * std::log(smax / smin));
+    double a = sc.ode ? 0.5 * g * g * dt : g * g * dt;
+    double z = g * std::sqrt(dt);
+    if (sc.temp_sampling[i] != 1.0) {
+      const double T = sc.temp_sampling[i], psi = sc.temp_psi[i], sdat = sc.temp_sigma_data[i];
+      const double sigma_data = std::exp(sdat * std::log(smax) + (1 - sdat) * std::log(smin));
+      const double lambda = (sigma_data + sigma) / (sigma_data + sigma / T);
+      a = g * g * dt * (lambda + T * psi / 2);
+      z = g * std::sqrt(dt * (1 + psi));
+    }
+    cs = (float)a;
+    cz = zero_noise ? 0.f : (float)z;
+  };
+  PerturbArgs p{};
+  p.B = B; p.R = torsion ? c.nT / B : 0; p.tr = tr; p.rot = rot; p.tor = tor;
+  coeffs(s_tr, cfg.tr_sigma_min, cfg.tr_sigma_max, dt_tr, 0, p.c_tr_s, p.c_tr_z);
+  coeffs(s_rot, cfg.rot_sigma_min, cfg.rot_sigma_max, dt_rot, 1, p.c_rot_s, p.c_rot_z);
+  coeffs(s_tor, cfg.tor_sigma_min, cfg.tor_sigma_max, dt_tor, 2, p.c_tor_s, p.c_tor_z);
+  if (!zero_noise) {
+    p.z_tr = sc.z_tr ? sc.z_tr + (size_t)k * B * 3 : nullptr;
+    p.z_rot = sc.z_rot ? sc.z_rot + (size_t)k * B * 3 : nullptr;
+    p.z_tor = sc.z_tor ? sc.z_tor + (size_t)k * c.nT : nullptr;
+    p.use_rng = 1;
+  }
+  p.seed = sc.seed; p.sample_ids = ids_dev; p.step = k;
+  if (c.layout) launch_perturb_grouped(p, c.G, c.grp_ptr, c.tor_ptr, c.tor_batch, s);
+  else launch_perturb(p, s);
+}
+
+static void check_sample_cfg(Model& m, const ddmi_sample_cfg& sc) {
+  DDMI_REQUIRE(sc.inference_steps > 0 && sc.tr_schedule && sc.rot_schedule && sc.tor_schedule, DDMI_ERR_ARG, "bad schedule");
+  DDMI_REQUIRE(m.cx->uniform || m.cx->layout, DDMI_ERR_STATE,
+               "the step loop needs a batch of copies of one complex, or ddmi_set_batch_layout for a batch of several");
+}
+
+void perturb(Model& m, float* tr, float* rot, float* tor, const ddmi_sample_cfg& sc, int k, hipStream_t s) {
+  DDMI_REQUIRE(m.has_complex, DDMI_ERR_STATE, "ddmi_set_complex must precede ddmi_perturb");
+  check_sample_cfg(m, sc);
+  DDMI_REQUIRE(k >= 0 && k < sc.inference_steps, DDMI_ERR_ARG, "step index out of range");
+  perturb_step(m, tr, rot, tor, sc, k, upload_sample_ids(m, sc.sample_ids, s), s);
+}
+
+void sample(Model& m, float* lig_pos, const ddmi_sample_cfg& sc, hipStream_t s) {
+  DDMI_REQUIRE(m.has_complex, DDMI_ERR_STATE, "ddmi_set_complex must precede ddmi_sample");
+  check_sample_cfg(m, sc);
+  Cx& c = *m.cx;
+  const ddmi_config& cfg = m.cfg;
+  const int steps = sc.inference_steps, B = c.B;
+  const bool torsion = !cfg.no_torsion && c.nT > 0;
+  struct CropGuard {   // the per-step crop must not outlive the loop, also when a step throws
+    Model& m; double saved;
+    ~CropGuard() { m.crop_cutoff = saved; }
+  } crop_guard{m, m.crop_cutoff};
+  if (!c.s_t) c.s_t = m.cpool.alloc<float>((size_t)3 * B * STEP_TIMES_MAX);
+  const long long* ids_dev = upload_sample_ids(m, sc.sample_ids, s);
+  const bool times_once = steps <= STEP_TIMES_MAX;   // set_time of every step in ONE launch in front of the loop (one launch less per forward)
+  if (times_once) {
+    StepTimes st{};
+    st.steps = steps;
+    for (int k = 0; k < steps; ++k) { st.t[3 * k] = (float)sc.tr_schedule[k]; st.t[3 * k + 1] = (float)sc.rot_schedule[k]; st.t[3 * k + 2] = (float)sc.tor_schedule[k]; }
+    launch_fill_times_all(c.s_t, B, st, s);
+  }
+  for (int k = 0; k < steps; ++k) {
+    const double t_tr = sc.tr_schedule[k], t_rot = sc.rot_schedule[k], t_tor = sc.tor_schedule[k];
+    const double s_tr = std::pow((double)cfg.tr_sigma_min, 1 - t_tr) * std::pow((double)cfg.tr_sigma_max, t_tr);
+    float* tk = times_once ? c.s_t + (size_t)k * 3 * B : c.s_t;
+    if (!times_once) launch_fill_times(tk, B, (float)t_tr, (float)t_rot, (float)t_tor, s);   // set_time for this step
+    m.crop_cutoff = sc.use_crop ? s_tr * 3.0 + sc.crop_beyond : 0.0;   // sampling.py:107
+    // (Measured and dropped in round 4, profiles/r04_e7_ab.txt: the forward captured once as a HIP graph -- every launch argument
+    // of a forward is the same in every step -- and replayed per step.  A dependent-kernel boundary costs the same inside a graph
+    // as between eager launches on this stack, and the replay's fixed cost is not hidden: 146.3 -> 145.4 poses/s at 40 poses,
+    // 102.2 -> 100.5 at 5.)
+    {
+      struct UniformT {   // every graph of the step has the same t (fill_times above): forward may share pose-invariant work
+        Model& m;
+        explicit UniformT(Model& mm) : m(mm) { m.uniform_t = true; }
+        ~UniformT() { m.uniform_t = false; }
+      } uniform_t{m};
+      forward(m, lig_pos, tk, tk + B, tk + 2 * B, c.s_tr, c.s_rot, torsion ? c.s_tor : nullptr, s);
+    }
+    perturb_step(m, c.s_tr, c.s_rot, torsion ? c.s_tor : nullptr, sc, k, ids_dev, s);
+#ifdef DDMI_PROFILING   // timing-only ablation builds produce garbage scores: DDMI_FREEZE_POSE keeps the graphs fixed (never in the shipped library)
+    static const bool freeze = getenv("DDMI_FREEZE_POSE") != nullptr;
+#else
+    constexpr bool freeze = false;
+#endif
+    if (!freeze) modify_conformer(m, lig_pos, c.s_tr, c.s_rot, torsion ? c.s_tor : nullptr, s);
+  }
+  c.x_last = nullptr;   // ddmi_sidechain_pred belongs to the ddmi_forward it follows: the loop's tables are not an answer to it
+}
+
+}  // namespace ddmi

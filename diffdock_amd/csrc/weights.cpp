@@ -452,7 +452,7 @@ static void commit_conv(Model& m, ConvW& L) {
     // static set, H % 16 != 0) runs the predicated variant, which walks classic 4-slot granules only.  So the list is built with
     // packing first and, when a generic granule turns up next to a packed one, once more without.
     for (int attempt = 0; attempt < 2; ++attempt) {
-    const bool allow_pack = m.fused_pack && attempt == 0;
+    const bool allow_pack = m.r.packed_granules && attempt == 0;
     bool any_packed = false;
     n_units = 0;
     fg.clear();
@@ -560,7 +560,7 @@ static void commit_conv(Model& m, ConvW& L) {
     // granule (36 + 24 MFMAs per step, one hidden-row pass, one epilogue); the slots feed DIFFERENT output channels (16*slot + w).
     bool any_generic = false;   // (a generic granule sends the whole layer to the compiler-scheduled kernel variant, which has no merged form)
     for (auto& G : fg) any_generic = any_generic || (!G.empty && G.shape == 0);
-    if (m.fused_tri && !any_generic && L.maxd <= 3 && m.cfg.sh_lmax <= 1 && L.H % 16 == 0) {
+    if (m.r.merged_granule && !any_generic && L.maxd <= 3 && m.cfg.sh_lmax <= 1 && L.H % 16 == 0) {
       for (size_t i = 0; i + 2 < fg.size(); ++i) {
         auto light = [&](const FGran& G, int w0) {
           return G.shape == 3 && !G.empty && !G.accumulate && G.dout == 1 && G.n_w == 16 && G.w0 == w0 && G.nslot == 4 &&

@@ -85,7 +85,8 @@ typedef struct ddmi_exec_options {
   int32_t tile_split_last;  /* workgroups per tile for the LAST chip-filling k_conv_fused launch of each stream in a layer (its final partial
                              * round of workgroups is the layer's straggler tail); 0 = as tile_split                                   */
   int32_t tile_split_rule;  /* automatic tile_split of a chip-filling group: 0 = cheapest schedule of ceil(tiles x split / CUs) rounds of
-                             * (granules per item + prologue) (round 6), 1 = one work item per tile (rounds 2-5)                        */
+                             * (granules per item + prologue) (round 6), 1 = one work item per tile (rounds 2-5),
+                             * 2 = as 0, and the same round model for groups of >= 32 tiles in layers where no group fills the chip (A/B) */
   int32_t group_order;      /* issue order of a layer's edge groups on their streams: 0 = [lig-lig, rec<-lig] | [lig<-rec, rec-rec];
                              * bit 0 = side stream reversed, bit 1 = main stream reversed (A/B knob)                                   */
   int32_t list_caps;        /* capacity of the virtual-node lists (= grid size of k_conv_fused): 0 = nodes + edges / 32 (up to 2 x the live
