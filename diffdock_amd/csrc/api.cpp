@@ -217,6 +217,13 @@ int ddmi_sample(ddmi_model* h, float* lig_pos, const ddmi_sample_cfg* cfg, ddmi_
   });
 }
 
+int ddmi_set_sample_record(ddmi_model* h, const ddmi_sample_record* r) {
+  return guard([&] {
+    DDMI_REQUIRE(h, DDMI_ERR_ARG, "null model");
+    set_sample_record(h->m, r);
+  });
+}
+
 int ddmi_perturb(ddmi_model* h, float* tr, float* rot, float* tor, const ddmi_sample_cfg* cfg, int step, ddmi_stream s) {
   return guard([&] {
     DDMI_REQUIRE(h && tr && rot && cfg, DDMI_ERR_ARG, "null argument");

@@ -572,6 +572,7 @@ void set_batch_layout(Model& m, const ddmi_batch_layout& l, hipStream_t s) {
   DDMI_CHECK_HIP(hipMemcpy(c.grp_ptr, l.group_ptr, (size_t)(G + 1) * sizeof(int), hipMemcpyHostToDevice));
   if (bytes) DDMI_CHECK_HIP(hipMemcpy(c.mask_all, l.mask_rotate, (size_t)bytes, hipMemcpyDeviceToDevice));
   c.layout = true; c.G = G;
+  c.rec_on = false;   // a record's nan_count rows were sized for the groups of before: set it again behind the layout
 }
 
 }  // namespace ddmi

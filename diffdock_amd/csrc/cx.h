@@ -89,6 +89,7 @@ struct Model::Cx {
   // sampler
   float *s_tr, *s_rot, *s_tor, *s_t = nullptr; long long* s_ids = nullptr;
   long long* s_ids_host = nullptr; hipEvent_t s_ids_ev = nullptr;   // pinned staging of the sample ids
+  bool rec_on = false; ddmi_sample_record rec{};   // ddmi_set_sample_record: caller-owned per-step arrays of the ddmi_sample loop
   ~Cx() { if (s_ids_host) (void)hipHostFree(s_ids_host); if (s_ids_ev) (void)hipEventDestroy(s_ids_ev); }
 };
 

@@ -87,15 +87,16 @@ __device__ void nan_fix(float* x, int n, float* red, int tid) {
 
 __global__ __launch_bounds__(256) void k_perturb(PerturbArgs a) {
   __shared__ float red[512];
-  __shared__ int flag;
+  __shared__ int flag, n_nan;
   const int tid = threadIdx.x;
-  if (tid == 0) flag = 0;
+  if (tid == 0) { flag = 0; n_nan = 0; }
   __syncthreads();
   for (int b = tid; b < a.B; b += 256) {
     const float m = (a.tr[3 * b] + a.tr[3 * b + 1] + a.tr[3 * b + 2]) / 3.f;
-    if (m != m) flag = 1;
+    if (m != m) { flag = 1; if (a.rec_nan) atomicAdd(&n_nan, 1); }
   }
   __syncthreads();
+  if (a.rec_nan && tid == 0) a.rec_nan[0] = n_nan;
   if (flag) {
     nan_fix(a.tr, 3 * a.B, red, tid);
     __syncthreads();
@@ -109,14 +110,19 @@ __global__ __launch_bounds__(256) void k_perturb(PerturbArgs a) {
     const long long sid = a.sample_ids ? a.sample_ids[b] : b;
     const float zt = a.z_tr ? a.z_tr[i] : (a.use_rng ? normal_draw(a.seed, sid, a.step, k) : 0.f);
     const float zr = a.z_rot ? a.z_rot[i] : (a.use_rng ? normal_draw(a.seed, sid, a.step, 3 + k) : 0.f);
-    a.tr[i] = mul_add_rn(a.c_tr_s, a.tr[i], a.c_tr_z, zt);
-    a.rot[i] = mul_add_rn(a.c_rot_s, a.rot[i], a.c_rot_z, zr);
+    const float st = a.tr[i], sr = a.rot[i];
+    if (a.rec_tr) a.rec_tr[i] = st;
+    if (a.rec_rot) a.rec_rot[i] = sr;
+    a.tr[i] = mul_add_rn(a.c_tr_s, st, a.c_tr_z, zt);
+    a.rot[i] = mul_add_rn(a.c_rot_s, sr, a.c_rot_z, zr);
   }
   for (int i = tid; i < a.B * a.R; i += 256) {
     const int b = i / a.R, k = i - b * a.R;
     const long long sid = a.sample_ids ? a.sample_ids[b] : b;
     const float z = a.z_tor ? a.z_tor[i] : (a.use_rng ? normal_draw(a.seed, sid, a.step, 6 + k) : 0.f);
-    a.tor[i] = mul_add_rn(a.c_tor_s, a.tor[i], a.c_tor_z, z);
+    const float st = a.tor[i];
+    if (a.rec_tor) a.rec_tor[i] = st;
+    a.tor[i] = mul_add_rn(a.c_tor_s, st, a.c_tor_z, z);
   }
 }
 void launch_perturb(const PerturbArgs& a, hipStream_t s) {
@@ -129,19 +135,20 @@ void launch_perturb(const PerturbArgs& a, hipStream_t s) {
 __global__ __launch_bounds__(256) void k_perturb_grouped(PerturbArgs a, const int* __restrict__ group_ptr,
                                                          const int* __restrict__ tor_ptr, const int* __restrict__ tor_batch) {
   __shared__ float red[512];
-  __shared__ int flag;
+  __shared__ int flag, n_nan;
   const int tid = threadIdx.x;
   const int b0 = group_ptr[blockIdx.x], b1 = group_ptr[blockIdx.x + 1];
   const int t0 = a.tor ? tor_ptr[b0] : 0, t1 = a.tor ? tor_ptr[b1] : 0;
   float* tr = a.tr + 3 * b0; float* rot = a.rot + 3 * b0;
   const int nb = b1 - b0;
-  if (tid == 0) flag = 0;
+  if (tid == 0) { flag = 0; n_nan = 0; }
   __syncthreads();
   for (int b = tid; b < nb; b += 256) {
     const float m = (tr[3 * b] + tr[3 * b + 1] + tr[3 * b + 2]) / 3.f;
-    if (m != m) flag = 1;
+    if (m != m) { flag = 1; if (a.rec_nan) atomicAdd(&n_nan, 1); }
   }
   __syncthreads();
+  if (a.rec_nan && tid == 0) a.rec_nan[blockIdx.x] = n_nan;
   if (flag) {
     nan_fix(tr, 3 * nb, red, tid);
     __syncthreads();
@@ -155,14 +162,19 @@ __global__ __launch_bounds__(256) void k_perturb_grouped(PerturbArgs a, const in
     const long long sid = a.sample_ids ? a.sample_ids[b] : b;
     const float zt = a.z_tr ? a.z_tr[i] : (a.use_rng ? normal_draw(a.seed, sid, a.step, k) : 0.f);
     const float zr = a.z_rot ? a.z_rot[i] : (a.use_rng ? normal_draw(a.seed, sid, a.step, 3 + k) : 0.f);
-    a.tr[i] = mul_add_rn(a.c_tr_s, a.tr[i], a.c_tr_z, zt);
-    a.rot[i] = mul_add_rn(a.c_rot_s, a.rot[i], a.c_rot_z, zr);
+    const float st = a.tr[i], sr = a.rot[i];
+    if (a.rec_tr) a.rec_tr[i] = st;
+    if (a.rec_rot) a.rec_rot[i] = sr;
+    a.tr[i] = mul_add_rn(a.c_tr_s, st, a.c_tr_z, zt);
+    a.rot[i] = mul_add_rn(a.c_rot_s, sr, a.c_rot_z, zr);
   }
   for (int i = t0 + tid; i < t1; i += 256) {
     const int b = tor_batch[i], k = i - tor_ptr[b];
     const long long sid = a.sample_ids ? a.sample_ids[b] : b;
     const float z = a.z_tor ? a.z_tor[i] : (a.use_rng ? normal_draw(a.seed, sid, a.step, 6 + k) : 0.f);
-    a.tor[i] = mul_add_rn(a.c_tor_s, a.tor[i], a.c_tor_z, z);
+    const float st = a.tor[i];
+    if (a.rec_tor) a.rec_tor[i] = st;
+    a.tor[i] = mul_add_rn(a.c_tor_s, st, a.c_tor_z, z);
   }
 }
 void launch_perturb_grouped(const PerturbArgs& a, int G, const int* group_ptr, const int* tor_ptr, const int* tor_batch,
@@ -243,8 +255,9 @@ __device__ void max_eigvec4(double* A, double* q) {
 }
 
 // one graph (64 threads): p [Nl][3] in place; tr / rot [3] and tor [R] (or nullptr) are the graph's updates, rot_u / rot_v
-// graph-local atom indices, mask_rotate its [R][Nl] block.  smem holds 6 * Nl + 16 floats.
-__device__ __forceinline__ void conformer_update(float* __restrict__ p, int Nl, int R, const int* __restrict__ rot_u,
+// graph-local atom indices, mask_rotate its [R][Nl] block.  smem holds 6 * Nl + 16 floats.  rp: nullptr, or the graph's [Nl][3]
+// block of a record row (ddmi_set_sample_record) that receives the final coordinates as well.
+__device__ __forceinline__ void conformer_update(float* __restrict__ p, float* __restrict__ rp, int Nl, int R, const int* __restrict__ rot_u,
                                                  const int* __restrict__ rot_v, const unsigned char* __restrict__ mask_rotate,
                                                  const float* __restrict__ tr, const float* __restrict__ rot,
                                                  const float* __restrict__ tor, float* smem) {
@@ -269,6 +282,7 @@ __device__ __forceinline__ void conformer_update(float* __restrict__ p, int Nl, 
   __syncthreads();
   if (tor == nullptr || R == 0) {
     for (int i = tid; i < 3 * Nl; i += 64) p[i] = rigid[i];
+    if (rp) for (int i = tid; i < 3 * Nl; i += 64) rp[i] = rigid[i];
     return;
   }
   for (int i = tid; i < 3 * Nl; i += 64) flex[i] = rigid[i];
@@ -319,7 +333,10 @@ __device__ __forceinline__ void conformer_update(float* __restrict__ p, int Nl, 
   __syncthreads();
   for (int a = tid; a < Nl; a += 64) {
     const float x = flex[3 * a], y = flex[3 * a + 1], z = flex[3 * a + 2];
-    for (int k = 0; k < 3; ++k) p[3 * a + k] = (sc[3 + 3 * k] * x + sc[4 + 3 * k] * y + sc[5 + 3 * k] * z) + sc[12 + k];
+    float out[3];
+    for (int k = 0; k < 3; ++k) out[k] = (sc[3 + 3 * k] * x + sc[4 + 3 * k] * y + sc[5 + 3 * k] * z) + sc[12 + k];
+    for (int k = 0; k < 3; ++k) p[3 * a + k] = out[k];
+    if (rp) for (int k = 0; k < 3; ++k) rp[3 * a + k] = out[k];
   }
 }
 // block (64 threads) per sample
@@ -327,10 +344,10 @@ __global__ __launch_bounds__(64) void k_modify_conformer(float* __restrict__ pos
                                                          const int* __restrict__ rot_u, const int* __restrict__ rot_v,
                                                          const unsigned char* __restrict__ mask_rotate,
                                                          const float* __restrict__ tr, const float* __restrict__ rot,
-                                                         const float* __restrict__ tor) {
+                                                         const float* __restrict__ tor, float* __restrict__ rec_pos) {
   DDMI_DYN_SMEM(float, smem);
   const int b = blockIdx.x;
-  conformer_update(pos + (size_t)b * Nl * 3, Nl, R, rot_u, rot_v, mask_rotate, tr + 3 * b, rot + 3 * b,
+  conformer_update(pos + (size_t)b * Nl * 3, rec_pos ? rec_pos + (size_t)b * Nl * 3 : nullptr, Nl, R, rot_u, rot_v, mask_rotate, tr + 3 * b, rot + 3 * b,
                    tor ? tor + (size_t)b * R : nullptr, smem);
 }
 // block (64 threads) per graph of a batch of different complexes (ddmi_set_batch_layout)
@@ -339,29 +356,29 @@ __global__ __launch_bounds__(64) void k_modify_conformer_ragged(float* __restric
                                                                 const int* __restrict__ rot_v, const long long* __restrict__ mask_off,
                                                                 const unsigned char* __restrict__ mask_rotate,
                                                                 const float* __restrict__ tr, const float* __restrict__ rot,
-                                                                const float* __restrict__ tor) {
+                                                                const float* __restrict__ tor, float* __restrict__ rec_pos) {
   DDMI_DYN_SMEM(float, smem);
   const int b = blockIdx.x;
   const int a0 = lig_ptr[b], t0 = tor_ptr[b];
   const int R = tor ? tor_ptr[b + 1] - t0 : 0;
-  conformer_update(pos + (size_t)a0 * 3, lig_ptr[b + 1] - a0, R, rot_u + t0, rot_v + t0, R ? mask_rotate + mask_off[b] : nullptr,
+  conformer_update(pos + (size_t)a0 * 3, rec_pos ? rec_pos + (size_t)a0 * 3 : nullptr, lig_ptr[b + 1] - a0, R, rot_u + t0, rot_v + t0, R ? mask_rotate + mask_off[b] : nullptr,
                    tr + 3 * b, rot + 3 * b, R ? tor + t0 : nullptr, smem);
 }
 void launch_modify_conformer(float* pos, int B, int Nl, int R, const int* rot_u, const int* rot_v,
                              const unsigned char* mask_rotate, const float* tr, const float* rot, const float* tor,
-                             hipStream_t s) {
+                             float* rec_pos, hipStream_t s) {
   if (B <= 0) return;
   const size_t smem = (size_t)(6 * Nl + 16) * sizeof(float);
-  hipLaunchKernelGGL(k_modify_conformer, dim3(B), dim3(64), smem, s, pos, Nl, R, rot_u, rot_v, mask_rotate, tr, rot, tor);
+  hipLaunchKernelGGL(k_modify_conformer, dim3(B), dim3(64), smem, s, pos, Nl, R, rot_u, rot_v, mask_rotate, tr, rot, tor, rec_pos);
   DDMI_CHECK_HIP(hipGetLastError());
 }
 void launch_modify_conformer_ragged(float* pos, int B, int maxNl, const int* lig_ptr, const int* tor_ptr, const int* rot_u,
                                     const int* rot_v, const long long* mask_off, const unsigned char* mask_rotate, const float* tr,
-                                    const float* rot, const float* tor, hipStream_t s) {
+                                    const float* rot, const float* tor, float* rec_pos, hipStream_t s) {
   if (B <= 0) return;
   const size_t smem = (size_t)(6 * maxNl + 16) * sizeof(float);
   hipLaunchKernelGGL(k_modify_conformer_ragged, dim3(B), dim3(64), smem, s, pos, lig_ptr, tor_ptr, rot_u, rot_v, mask_off,
-                     mask_rotate, tr, rot, tor);
+                     mask_rotate, tr, rot, tor, rec_pos);
   DDMI_CHECK_HIP(hipGetLastError());
 }
 

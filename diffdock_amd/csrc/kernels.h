@@ -331,6 +331,9 @@ struct PerturbArgs {
   const float *z_tr, *z_rot, *z_tor;  // may be nullptr (zero noise)
   float c_tr_s, c_tr_z, c_rot_s, c_rot_z, c_tor_s, c_tor_z;
   int use_rng; unsigned long long seed; const long long* sample_ids; int step;
+  // ddmi_set_sample_record: row `step` of the caller's arrays, each nullptr when not recorded -- the scores behind the NaN guard
+  // ([B][3], [B][3], [n_tor], indexed as tr / rot / tor) and the poses per NaN-guard group whose mean tr score was NaN ([G])
+  float *rec_tr, *rec_rot, *rec_tor; int* rec_nan;
 };
 void launch_perturb(const PerturbArgs& a, hipStream_t s);
 // ddmi_set_batch_layout: one workgroup per NaN-guard group (graphs [group_ptr[g], group_ptr[g+1])); graph b's torsions are
@@ -345,13 +348,14 @@ constexpr int STEP_TIMES_MAX = 64;
 struct StepTimes { int steps; float t[3 * STEP_TIMES_MAX]; };   // (t_tr, t_rot, t_tor) of every step
 void launch_fill_times_all(float* t /* [steps][3][B] */, int B, const StepTimes& st, hipStream_t s);
 void launch_fill_times(float* t, int B, float t_tr, float t_rot, float t_tor, hipStream_t s);
+// rec_pos: nullptr, or a second [n_lig][3] array that receives the updated coordinates as well (a row of ddmi_sample_record.pos)
 void launch_modify_conformer(float* pos, int B, int Nl, int R, const int* rot_u, const int* rot_v,
                              const unsigned char* mask_rotate, const float* tr, const float* rot, const float* tor,
-                             hipStream_t s);
+                             float* rec_pos, hipStream_t s);
 // graphs of different complexes: graph b = atoms [lig_ptr[b], lig_ptr[b+1]), torsions [tor_ptr[b], tor_ptr[b+1]) with graph-local
 // rot_u / rot_v, mask block at mask_off[b] ([R_b][Nl_b]); maxNl sizes the LDS.  Same per-graph arithmetic as the uniform kernel.
 void launch_modify_conformer_ragged(float* pos, int B, int maxNl, const int* lig_ptr, const int* tor_ptr, const int* rot_u,
                                     const int* rot_v, const long long* mask_off, const unsigned char* mask_rotate, const float* tr,
-                                    const float* rot, const float* tor, hipStream_t s);
+                                    const float* rot, const float* tor, float* rec_pos, hipStream_t s);
 
 }  // namespace ddmi

@@ -170,7 +170,10 @@ void forward(Model& m, const float* lig_pos, const float* t_tr, const float* t_r
              float* rot_out, float* tor_out, hipStream_t s, float* conf_out = nullptr, float* atom_conf_out = nullptr);
 void sidechain_pred(Model& m, float* out, hipStream_t s);   // model(batch)[3] of the last forward (models/cg_model.py:397-402)
 // sample.cpp
-void modify_conformer(Model& m, float* lig_pos, const float* tr, const float* rot, const float* tor, hipStream_t s);
+// rec_pos: nullptr, or a row of ddmi_sample_record.pos that receives the updated coordinates as well
+void modify_conformer(Model& m, float* lig_pos, const float* tr, const float* rot, const float* tor, hipStream_t s,
+                      float* rec_pos = nullptr);
+void set_sample_record(Model& m, const ddmi_sample_record* r);   // nullptr = off
 void sample(Model& m, float* lig_pos, const ddmi_sample_cfg& sc, hipStream_t s);
 // NaN guard + score / noise combination of step k (utils/sampling.py:117-186) on score arrays, in place
 void perturb(Model& m, float* tr, float* rot, float* tor, const ddmi_sample_cfg& sc, int k, hipStream_t s);

@@ -8,12 +8,13 @@
 
 namespace ddmi {
 
-void modify_conformer(Model& m, float* lig_pos, const float* tr, const float* rot, const float* tor, hipStream_t s) {
+void modify_conformer(Model& m, float* lig_pos, const float* tr, const float* rot, const float* tor, hipStream_t s,
+                      float* rec_pos) {
   DDMI_REQUIRE(m.has_complex, DDMI_ERR_STATE, "ddmi_set_complex must precede ddmi_modify_conformer");
   Cx& c = *m.cx;
   if (c.layout) {
     launch_modify_conformer_ragged(lig_pos, c.B, c.maxNl, c.lig_ptr, c.tor_ptr, c.rot_lu, c.rot_lv, c.mask_off, c.mask_all, tr, rot,
-                                   c.nT > 0 ? tor : nullptr, s);
+                                   c.nT > 0 ? tor : nullptr, rec_pos, s);
     return;
   }
   DDMI_REQUIRE(c.uniform && c.Nl_one > 0, DDMI_ERR_STATE,
@@ -21,7 +22,19 @@ void modify_conformer(Model& m, float* lig_pos, const float* tr, const float* ro
   const bool torsion = tor != nullptr && c.R_one > 0;
   DDMI_REQUIRE(!torsion || c.mask_rotate, DDMI_ERR_STATE, "mask_rotate was not provided to ddmi_set_complex");
   launch_modify_conformer(lig_pos, c.B, c.Nl_one, torsion ? c.R_one : 0, c.rot_u, c.rot_v, c.mask_rotate, tr, rot,
-                          torsion ? tor : nullptr, s);
+                          torsion ? tor : nullptr, rec_pos, s);
+}
+
+void set_sample_record(Model& m, const ddmi_sample_record* r) {
+  if (!r) {
+    if (m.cx) m.cx->rec_on = false;
+    return;
+  }
+  DDMI_REQUIRE(r->struct_size == sizeof(ddmi_sample_record), DDMI_ERR_ARG, "ddmi_sample_record.struct_size does not match this library");
+  DDMI_REQUIRE(r->capacity_steps >= 1, DDMI_ERR_ARG, "ddmi_sample_record.capacity_steps must be positive");
+  DDMI_REQUIRE(m.has_complex, DDMI_ERR_STATE, "ddmi_set_complex must precede ddmi_set_sample_record");
+  m.cx->rec = *r;
+  m.cx->rec_on = true;
 }
 
 // Sample ids of the batch (keys of the counter-based generator) on the device: staged through a pinned host buffer, so
@@ -45,8 +58,9 @@ static const long long* upload_sample_ids(Model& m, const int64_t* ids, hipStrea
 
 // Step k of utils/sampling.py:117-186 on score arrays (in place): NaN guard, then score and noise coefficients evaluated on
 // the host in float64 exactly as the reference's 0-dim float64 tensors are.
+// rec: the record whose row k receives the guarded scores and the NaN counts (the ddmi_sample loop), or nullptr.
 static void perturb_step(Model& m, float* tr, float* rot, float* tor, const ddmi_sample_cfg& sc, int k,
-                         const long long* ids_dev, hipStream_t s) {
+                         const long long* ids_dev, hipStream_t s, const ddmi_sample_record* rec = nullptr) {
   Cx& c = *m.cx;
   const ddmi_config& cfg = m.cfg;
   const int steps = sc.inference_steps, B = c.B;
@@ -86,6 +100,12 @@ static void perturb_step(Model& m, float* tr, float* rot, float* tor, const ddmi
     p.use_rng = 1;
   }
   p.seed = sc.seed; p.sample_ids = ids_dev; p.step = k;
+  if (rec) {
+    if (rec->tr) p.rec_tr = rec->tr + (size_t)k * B * 3;
+    if (rec->rot) p.rec_rot = rec->rot + (size_t)k * B * 3;
+    if (rec->tor && torsion) p.rec_tor = rec->tor + (size_t)k * c.nT;
+    if (rec->nan_count) p.rec_nan = rec->nan_count + (size_t)k * (c.layout ? c.G : 1);
+  }
   if (c.layout) launch_perturb_grouped(p, c.G, c.grp_ptr, c.tor_ptr, c.tor_batch, s);
   else launch_perturb(p, s);
 }
@@ -110,6 +130,9 @@ void sample(Model& m, float* lig_pos, const ddmi_sample_cfg& sc, hipStream_t s) 
   const ddmi_config& cfg = m.cfg;
   const int steps = sc.inference_steps, B = c.B;
   const bool torsion = !cfg.no_torsion && c.nT > 0;
+  const ddmi_sample_record* rec = c.rec_on ? &c.rec : nullptr;
+  DDMI_REQUIRE(!rec || rec->capacity_steps >= steps, DDMI_ERR_ARG,
+               "ddmi_sample_record.capacity_steps = " + std::to_string(rec ? rec->capacity_steps : 0) + " < inference_steps = " + std::to_string(steps));
   struct CropGuard {   // the per-step crop must not outlive the loop, also when a step throws
     Model& m; double saved;
     ~CropGuard() { m.crop_cutoff = saved; }
@@ -141,13 +164,14 @@ void sample(Model& m, float* lig_pos, const ddmi_sample_cfg& sc, hipStream_t s) 
       } uniform_t{m};
       forward(m, lig_pos, tk, tk + B, tk + 2 * B, c.s_tr, c.s_rot, torsion ? c.s_tor : nullptr, s);
     }
-    perturb_step(m, c.s_tr, c.s_rot, torsion ? c.s_tor : nullptr, sc, k, ids_dev, s);
+    perturb_step(m, c.s_tr, c.s_rot, torsion ? c.s_tor : nullptr, sc, k, ids_dev, s, rec);
 #ifdef DDMI_PROFILING   // timing-only ablation builds produce garbage scores: DDMI_FREEZE_POSE keeps the graphs fixed (never in the shipped library)
     static const bool freeze = getenv("DDMI_FREEZE_POSE") != nullptr;
 #else
     constexpr bool freeze = false;
 #endif
-    if (!freeze) modify_conformer(m, lig_pos, c.s_tr, c.s_rot, torsion ? c.s_tor : nullptr, s);
+    if (!freeze) modify_conformer(m, lig_pos, c.s_tr, c.s_rot, torsion ? c.s_tor : nullptr, s,
+                                  rec && rec->pos ? rec->pos + (size_t)k * c.nL * 3 : nullptr);
   }
   c.x_last = nullptr;   // ddmi_sidechain_pred belongs to the ddmi_forward it follows: the loop's tables are not an answer to it
 }

@@ -134,6 +134,11 @@ class BatchLayout(C.Structure):   # ddmi_batch_layout (include/ddmi.h)
                 ("mask_rotate_bytes", C.c_int64)]
 
 
+class SampleRecord(C.Structure):   # ddmi_sample_record (include/ddmi.h)
+    _fields_ = [("struct_size", C.c_uint32), ("capacity_steps", C.c_int32), ("pos", C.c_void_p), ("tr", C.c_void_p),
+                ("rot", C.c_void_p), ("tor", C.c_void_p), ("nan_count", C.c_void_p)]
+
+
 def make_config(cfg) -> Config:
     c = Config()
     for name, _ in Config._fields_:
@@ -177,6 +182,7 @@ _DECLS = {
     "ddmi_set_crop_cutoff": (C.c_int, [C.c_void_p, C.c_float]),
     "ddmi_modify_conformer": (C.c_int, [C.c_void_p] + [C.c_void_p] * 4 + [C.c_void_p]),
     "ddmi_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(SampleCfg), C.c_void_p]),
+    "ddmi_set_sample_record": (C.c_int, [C.c_void_p, C.POINTER(SampleRecord)]),
     "ddmi_perturb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SampleCfg), C.c_int, C.c_void_p]),
     "ddmi_debug_shape": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ddmi_debug_read": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -233,6 +239,20 @@ def set_batch_layout(lib, handle, group_sizes, mask_rotate, stream=None):
     lay.mask_rotate = None if mask_rotate is None else mask_rotate.data_ptr()
     lay.mask_rotate_bytes = 0 if mask_rotate is None else mask_rotate.numel()
     check(lib, lib.ddmi_set_batch_layout(handle, C.byref(lay), stream))
+
+
+def set_sample_record(lib, handle, capacity_steps=0, pos=None, tr=None, rot=None, tor=None, nan_count=None, off=False):
+    """ddmi_set_sample_record: the device tensors (float32 pos / tr / rot / tor, int32 nan_count, `capacity_steps` rows each, None =
+    not recorded) that the following ddmi_sample calls on the handle fill; `off=True` passes NULL.  The caller keeps the tensors
+    alive until the enqueued steps have run."""
+    if off:
+        check(lib, lib.ddmi_set_sample_record(handle, None))
+        return
+    r = SampleRecord()
+    r.struct_size, r.capacity_steps = C.sizeof(SampleRecord), int(capacity_steps)
+    for name, t in (("pos", pos), ("tr", tr), ("rot", rot), ("tor", tor), ("nan_count", nan_count)):
+        setattr(r, name, None if t is None or t.numel() == 0 else t.data_ptr())
+    check(lib, lib.ddmi_set_sample_record(handle, C.byref(r)))
 
 
 def wigner_3j(lib, l1, l2, l3):

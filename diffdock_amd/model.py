@@ -14,6 +14,7 @@ import ctypes as C
 import math
 import os
 import weakref
+from types import SimpleNamespace
 from typing import Dict, Optional
 
 import numpy as np
@@ -344,20 +345,48 @@ class MIScoreModel:
 
     def sample_batch(self, data, inference_steps, schedules, noise=None, seed=0, sample_ids=None, ode=False,
                      no_random=False, no_final_step_noise=False, temp_sampling=1.0, temp_psi=0.0, temp_sigma_data=0.5,
-                     crop_beyond=None, groups=None):
+                     crop_beyond=None, groups=None, record=None):
         """The whole step loop of sampling() (utils/sampling.py:96-191) for one collated batch, on the device.  `groups` = graphs
-        per NaN-guard group in batch order (default: the whole batch is one group, as one sampling() batch)."""
+        per NaN-guard group in batch order (default: the whole batch is one group, as one sampling() batch).
+
+        `record` = True, or a subset of {"pos", "scores", "nan"}: the kernels of the loop also write what they hold at every step
+        into device tensors (ddmi_set_sample_record; no extra launch or synchronisation, final poses bit-identical), and the call
+        returns (pos, rec) with rec.pos [steps, n_lig, 3] the poses AFTER step k, rec.tr / rec.rot [steps, B, 3] and rec.tor
+        [steps, n_tor] the scores of step k behind the NaN guard, rec.nan_count [steps, G] int32 the poses per NaN-guard group
+        whose mean tr score was NaN; parts not requested are None.  Without `record` the return value is the poses alone."""
         self._ensure_complex(data)
         self._ensure_layout(groups)
         pos = data["ligand"].pos.to(self.device, torch.float32).contiguous().clone()
         sc, keep = self._sample_cfg(inference_steps, schedules, noise, seed, sample_ids, ode, no_random, no_final_step_noise,
                                     temp_sampling, temp_psi, temp_sigma_data, crop_beyond)
-        _lib.check(self.lib, self.lib.ddmi_sample(self._h, _ptr(pos), C.byref(sc), self._stream()))
+        rec = None
+        if record:
+            rec = self._new_record(inference_steps, {"pos", "scores", "nan"} if record is True else set(record))
+            _lib.set_sample_record(self.lib, self._h, inference_steps, rec.pos, rec.tr, rec.rot, rec.tor, rec.nan_count)
+        try:
+            _lib.check(self.lib, self.lib.ddmi_sample(self._h, _ptr(pos), C.byref(sc), self._stream()))
+        finally:
+            if rec is not None:
+                _lib.set_sample_record(self.lib, self._h, off=True)
         if noise is not None and self.device.type == "cuda":   # the injected draws must outlive the enqueued steps
             for z in keep[2]:
                 if z is not None:
                     z.record_stream(torch.cuda.current_stream(self.device))
-        return pos
+        return pos if rec is None else (pos, rec)
+
+    def _new_record(self, steps, parts):
+        """Device tensors of a per-step record of the current complex (see sample_batch); zero-filled."""
+        if not parts <= {"pos", "scores", "nan"}:
+            raise ValueError(f"record: True or a subset of 'pos', 'scores', 'nan', got {sorted(parts)}")
+        dev, B = self.device, self._B
+        n_tor = 0 if self.cfg.no_torsion else self._n_tor
+        G = len(self._layout) if self._layout is not None else 1
+        z = lambda *shape, dtype=torch.float32: torch.zeros(*shape, dtype=dtype, device=dev)
+        sc = "scores" in parts
+        return SimpleNamespace(pos=z(steps, self._n_lig, 3) if "pos" in parts else None,
+                               tr=z(steps, B, 3) if sc else None, rot=z(steps, B, 3) if sc else None,
+                               tor=z(steps, n_tor) if sc else None,
+                               nan_count=z(steps, G, dtype=torch.int32) if "nan" in parts else None)
 
     def perturb(self, data, tr_score, rot_score, tor_score, t_idx, inference_steps, schedules, noise=None, seed=0,
                 sample_ids=None, ode=False, no_random=False, no_final_step_noise=False, temp_sampling=1.0, temp_psi=0.0,

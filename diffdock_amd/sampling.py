@@ -7,16 +7,83 @@ Differences, all documented: the Gaussian draws come from a counter-based genera
 (seed, global sample index, step, component) instead of the global torch RNG (so that a run sharded over GPUs
 reproduces the single-GPU trajectories), or are injected through `noise=`; the confidence model is called after each
 batch exactly as in the reference (sampling.py:208-227: fresh ligand positions copied into the confidence graphs,
-t = 0) when it is a confidence-mode model of the built classes; visualisation hooks / full trajectories / feature
-returns are not on the built path and raise NotImplementedError.  Per-step `crop_beyond` (sampling.py:104-109) runs on the device as a residue
+t = 0) when it is a confidence-mode model of the built classes.  Per-step `crop_beyond` (sampling.py:104-109) runs on the device as a residue
 mask + contact-graph re-compaction instead of the reference's deepcopy / to_data_list / from_data_list round trip.
+
+`visualization_list` (sampling.py:193-206) is fed call for call as the reference feeds it, from the per-step record the device
+loop writes (MIScoreModel.sample_batch(record=...)); `return_full_trajectory=True` returns the per-step poses as a third value
+(see sampling()); the reference's NaN warning (sampling.py:117-124) is emitted through `logging` after each batch's loop from the
+recorded per-step counts.  `pivot` and `return_features` raise NotImplementedError: the reference asserts them away too (:81).
 """
 from __future__ import annotations
+
+import logging
 
 import numpy as np
 import torch
 
 from .hetero import HeteroBatch, set_time
+
+
+logger = logging.getLogger(__name__)
+
+
+def _check_hooks(model, want_steps, pivot, return_features):
+    if return_features or pivot:
+        raise NotImplementedError("pivot / feature returns are outside the built path (the reference asserts them away as well, "
+                                  "utils/sampling.py:81)")
+    if want_steps and not (hasattr(model, "sample_batch") or hasattr(model, "perturb")):
+        raise NotImplementedError("per-step poses (visualization_list / return_full_trajectory) need a model with sample_batch "
+                                  "(the device loop) or with perturb / modify_conformer_batch (the step-wise loop)")
+
+
+def _sample_batch(model, want_steps, *args, **kw):
+    """model.sample_batch with the per-step record -> (pos, step_pos or None, nan_count or None).  A model whose sample_batch
+    does not take `record` (the signature of before the record) still samples: no NaN warnings, and per-step poses raise."""
+    import inspect
+    params = inspect.signature(model.sample_batch).parameters
+    if "record" not in params and not any(p.kind is p.VAR_KEYWORD for p in params.values()):
+        if want_steps:
+            raise NotImplementedError("per-step poses (visualization_list / return_full_trajectory) on the device loop need a "
+                                      "model.sample_batch that takes `record` (MIScoreModel.sample_batch); native_loop=False "
+                                      "runs the step-wise loop instead")
+        return model.sample_batch(*args, **kw), None, None
+    pos, rec = model.sample_batch(*args, record={"nan", "pos"} if want_steps else {"nan"}, **kw)
+    return pos, rec.pos, rec.nan_count
+
+
+def _warn_nans(nan_count, names, batch_numbers, sizes):
+    """The reference's warning (utils/sampling.py:117-124) for every step and NaN-guard group of one device batch whose guard
+    fired.  nan_count: [steps, G] counts (one device-to-host copy here, after the loop); names / batch_numbers / sizes: the
+    complex name, 1-based sampling() batch number and number of poses of each group."""
+    if nan_count is None:
+        return
+    nan_count = torch.as_tensor(nan_count).detach().cpu()
+    for t_idx, g in torch.nonzero(nan_count).tolist():
+        logger.warning(f"Complex {names[g]} Batch {batch_numbers[g]} Inference Iteration {t_idx}: "
+                       f"{int(nan_count[t_idx, g])} / {sizes[g]} samples failed")
+
+
+def _complex_name(graph):
+    name = getattr(graph, "name", "?")
+    return name[0] if isinstance(name, list) else name
+
+
+def _visualise_steps(visualization_list, data_list, lo, step_pos, bounds, first_step=0):
+    """utils/sampling.py:193-198 for one sampling() batch: step_pos [steps, atoms, 3] on the host = the poses after steps
+    first_step, first_step + 1, ..., bounds[i] = the atom range of pose lo + i in it."""
+    for row in range(step_pos.shape[0]):
+        for i, (a0, a1) in enumerate(bounds):
+            visualization_list[lo + i].add(step_pos[row, a0:a1] + data_list[lo + i].original_center.detach().cpu(),
+                                           part=1, order=first_step + row + 2)
+
+
+def _visualise_final(visualization_list, data_list):
+    """utils/sampling.py:203-206: after every batch the WHOLE list receives its entry's current pose with order=2 -- the poses
+    of batches not yet sampled are their initial ones (kept as the reference does it)."""
+    for idx, visualization in enumerate(visualization_list):
+        visualization.add(data_list[idx]["ligand"].pos.detach().cpu() + data_list[idx].original_center.detach().cpu(),
+                          part=1, order=2)
 
 
 def _batches(data_list, batch_size):
@@ -104,8 +171,14 @@ def sampling(data_list, model, inference_steps, tr_schedule, rot_schedule, tor_s
              confidence_data_list=None, confidence_model_args=None, t_schedule=None, batch_size=32,
              no_final_step_noise=False, pivot=None, return_full_trajectory=False, temp_sampling=1.0, temp_psi=0.0,
              temp_sigma_data=0.5, return_features=False, seed=0, noise=None, sample_id_offset=0, native_loop=True):
-    if visualization_list is not None or return_full_trajectory or return_features or pivot:
-        raise NotImplementedError("visualisation / trajectories / feature returns are outside the built path")
+    """utils/sampling.py:69-240.  Returns (data_list, confidence), or with `return_full_trajectory=True`
+    (data_list, confidence, trajectory): float32 [inference_steps + 1, N, n, 3] on the poses' device, row 0 the initial poses,
+    row k + 1 the poses after step k, coordinates centred as the model sees them (no original_center added; the reference
+    asserts this flag away and never fills its `trajectory`).  `visualization_list`: one object with .add(coords, part, order)
+    per pose, fed as utils/sampling.py:193-206 feeds PDBFile objects (host tensors, original_center added)."""
+    want_steps = visualization_list is not None or return_full_trajectory
+    _check_hooks(model, want_steps, pivot, return_features)
+    trajectory = [] if return_full_trajectory else None
     confidence = [] if confidence_model is not None else None
     conf_batches = None
     conf_crop = getattr(confidence_model_args, "crop_beyond", None) if confidence_model_args is not None else None
@@ -128,13 +201,19 @@ def sampling(data_list, model, inference_steps, tr_schedule, rot_schedule, tor_s
             z = None
             if noise is not None:
                 z = (noise[0][:, lo:lo + b], noise[1][:, lo:lo + b], noise[2][:, lo * R:(lo + b) * R])
+            pos0 = batch["ligand"].pos
+            bounds = [(i * n, (i + 1) * n) for i in range(b)]
             if native_loop and hasattr(model, "sample_batch"):
-                pos = model.sample_batch(batch, inference_steps, schedules, noise=z, seed=seed, sample_ids=ids, ode=ode,
-                                         no_random=no_random, no_final_step_noise=no_final_step_noise,
-                                         temp_sampling=temp_sampling, temp_psi=temp_psi, temp_sigma_data=temp_sigma_data,
-                                         crop_beyond=crop)
+                # the device loop records the NaN counts always ([steps, 1] ints) and the per-step poses when they are asked for
+                pos, step_pos, nan_count = _sample_batch(
+                    model, want_steps, batch, inference_steps, schedules, noise=z, seed=seed, sample_ids=ids, ode=ode,
+                    no_random=no_random, no_final_step_noise=no_final_step_noise, temp_sampling=temp_sampling, temp_psi=temp_psi,
+                    temp_sigma_data=temp_sigma_data, crop_beyond=crop)
+                if visualization_list is not None:   # one read of the device record after the loop
+                    _visualise_steps(visualization_list, data_list, lo, step_pos.detach().cpu(), bounds)
             else:   # step-wise: model(batch) per step, exactly the reference's loop structure
                 pos = batch["ligand"].pos
+                step_list, nan_list = [], []
                 try:
                     for t_idx in range(inference_steps):
                         set_time(batch, schedules[0][t_idx], schedules[1][t_idx], schedules[2][t_idx], b, device=pos.device)
@@ -143,18 +222,31 @@ def sampling(data_list, model, inference_steps, tr_schedule, rot_schedule, tor_s
                             t = float(schedules[0][t_idx])
                             model.set_crop_cutoff(cfg.tr_sigma_min ** (1 - t) * cfg.tr_sigma_max ** t * 3 + crop)
                         tr, rot, tor = model(batch)[:3]
+                        nan_list.append(torch.isnan(tr.mean(-1)).sum().reshape(1))
                         # NaN guard + update formulas (sampling.py:117-186) on the device, same kernel as the native loop
                         trp, rotp, torp = model.perturb(batch, tr, rot, tor, t_idx, inference_steps, schedules, noise=z, seed=seed,
                                                         sample_ids=ids, ode=ode, no_random=no_random,
                                                         no_final_step_noise=no_final_step_noise, temp_sampling=temp_sampling,
                                                         temp_psi=temp_psi, temp_sigma_data=temp_sigma_data)
                         pos = model.modify_conformer_batch(pos, batch, trp, rotp, torp)
+                        if visualization_list is not None:   # sampling.py:193-198, fed as the loop goes
+                            _visualise_steps(visualization_list, data_list, lo, pos.detach().cpu()[None], bounds, first_step=t_idx)
+                        if return_full_trajectory:
+                            step_list.append(pos)
                 finally:
                     if crop is not None:
                         model.set_crop_cutoff(None)
+                step_pos = torch.stack(step_list) if step_list else None
+                nan_count = torch.stack(nan_list)
+            _warn_nans(nan_count, [_complex_name(chunk[0])], [lo // batch_size + 1], [b])
+            if return_full_trajectory:
+                trajectory.append(torch.cat([pos0.to(step_pos.device, torch.float32)[None], step_pos], 0)
+                                  .reshape(inference_steps + 1, b, n, 3))
             pos = pos.reshape(b, n, 3)
             for i in range(b):
                 data_list[lo + i]["ligand"].pos = pos[i]
+            if visualization_list is not None:
+                _visualise_final(visualization_list, data_list)
             if confidence_model is not None:   # sampling.py:208-227
                 if conf_batches is not None:
                     cgraphs = next(conf_batches)
@@ -195,6 +287,8 @@ def sampling(data_list, model, inference_steps, tr_schedule, rot_schedule, tor_s
                 confidence.append(out[0] if isinstance(out, tuple) else out)
     if confidence is not None:
         confidence = torch.nan_to_num(torch.cat(confidence, dim=0), nan=-1000)
+    if return_full_trajectory:
+        return data_list, confidence, torch.cat(trajectory, 1)
     return data_list, confidence
 
 
@@ -227,12 +321,21 @@ def sample_complexes(complex_data_lists, model, inference_steps, tr_schedule, ro
 
     Sample ids: pose i of complex k uses sample id offset_k + i, offset_k = the number of poses of the complexes before it, so
     complex k gets exactly the draws of sampling(complex_data_lists[k], ..., seed=seed, sample_id_offset=offset_k).
-    `noise` = one (z_tr [steps,N_k,3], z_rot [steps,N_k,3], z_tor [steps,N_k*R_k]) per complex, laid out as sampling()'s."""
-    if visualization_list is not None or return_full_trajectory or return_features or pivot:
-        raise NotImplementedError("visualisation / trajectories / feature returns are outside the built path")
+    `noise` = one (z_tr [steps,N_k,3], z_rot [steps,N_k,3], z_tor [steps,N_k*R_k]) per complex, laid out as sampling()'s.
+
+    `visualization_list` = one visualisation list per complex; each receives exactly the calls sampling() of that complex alone
+    makes (utils/sampling.py:193-206, a chunk at a time: its steps, then the order=2 pass over the complex's whole list), fed
+    after each device batch's loop on both routes.  `return_full_trajectory=True` appends a third entry to every complex's
+    tuple: float32 [inference_steps + 1, N_k, n_k, 3] as sampling() defines it.  The NaN warning names the complex and the
+    sampling() batch number of the chunk whose guard fired."""
+    want_steps = visualization_list is not None or return_full_trajectory
+    _check_hooks(model, want_steps, pivot, return_features)
     if max_batch_graphs < 1 or batch_size < 1:
         raise ValueError("batch_size and max_batch_graphs must be positive")
     lists = list(complex_data_lists)
+    if visualization_list is not None and len(visualization_list) != len(lists):
+        raise ValueError("visualization_list: one list per complex")
+    trajectory = [[] for _ in lists] if return_full_trajectory else None
     if noise is not None and len(noise) != len(lists):
         raise ValueError("noise: one (z_tr, z_rot, z_tor) per complex")
     if confidence_data_lists is not None and len(confidence_data_lists) != len(lists):
@@ -262,13 +365,16 @@ def sample_complexes(complex_data_lists, model, inference_steps, tr_schedule, ro
                     zk = noise[k]
                     parts.append((zk[0][:, lo:lo + len(chunk)], zk[1][:, lo:lo + len(chunk)], zk[2][:, lo * R:(lo + len(chunk)) * R]))
                 z = tuple(torch.cat([torch.as_tensor(p[i]) for p in parts], 1) for i in range(3))
+            pos0 = batch["ligand"].pos
             if native_loop and hasattr(model, "sample_batch"):
-                pos = model.sample_batch(batch, inference_steps, schedules, noise=z, seed=seed, sample_ids=ids, ode=ode,
-                                         no_random=no_random, no_final_step_noise=no_final_step_noise,
-                                         temp_sampling=temp_sampling, temp_psi=temp_psi, temp_sigma_data=temp_sigma_data,
-                                         crop_beyond=crop, groups=sizes)
+                pos, step_pos, nan_count = _sample_batch(
+                    model, want_steps, batch, inference_steps, schedules, noise=z, seed=seed, sample_ids=ids, ode=ode,
+                    no_random=no_random, no_final_step_noise=no_final_step_noise, temp_sampling=temp_sampling, temp_psi=temp_psi,
+                    temp_sigma_data=temp_sigma_data, crop_beyond=crop, groups=sizes)
             else:   # step-wise, as sampling()'s: the NaN guard of model.perturb runs per chunk
                 pos = batch["ligand"].pos
+                step_list, nan_list = [], []
+                group_of = torch.repeat_interleave(torch.arange(len(sizes)), torch.as_tensor(sizes))
                 try:
                     for t_idx in range(inference_steps):
                         set_time(batch, schedules[0][t_idx], schedules[1][t_idx], schedules[2][t_idx], b, device=pos.device)
@@ -277,21 +383,41 @@ def sample_complexes(complex_data_lists, model, inference_steps, tr_schedule, ro
                             t = float(schedules[0][t_idx])
                             model.set_crop_cutoff(cfg.tr_sigma_min ** (1 - t) * cfg.tr_sigma_max ** t * 3 + crop)
                         tr, rot, tor = model(batch)[:3]
+                        failed = torch.isnan(tr.mean(-1)).to(torch.int64)
+                        nan_list.append(torch.zeros(len(sizes), dtype=torch.int64, device=failed.device)
+                                        .index_add_(0, group_of.to(failed.device), failed))
                         trp, rotp, torp = model.perturb(batch, tr, rot, tor, t_idx, inference_steps, schedules, noise=z, seed=seed,
                                                         sample_ids=ids, ode=ode, no_random=no_random,
                                                         no_final_step_noise=no_final_step_noise, temp_sampling=temp_sampling,
                                                         temp_psi=temp_psi, temp_sigma_data=temp_sigma_data, groups=sizes)
                         pos = model.modify_conformer_batch(pos, batch, trp, rotp, torp)
+                        if want_steps:
+                            step_list.append(pos)
                 finally:
                     if crop is not None:
                         model.set_crop_cutoff(None)
+                step_pos = torch.stack(step_list) if step_list else None
+                nan_count = torch.stack(nan_list)
+            _warn_nans(nan_count, [_complex_name(chunk[0]) for _, _, chunk in members],
+                       [lo // batch_size + 1 for _, lo, _ in members], sizes)
             n_l = [int(g["ligand"].pos.shape[0]) for g in graphs]
             pos_g = torch.split(pos, n_l)
+            atom_ptr = np.concatenate([[0], np.cumsum(n_l)]).astype(int).tolist()
+            step_host = step_pos.detach().cpu() if visualization_list is not None else None
             j = 0
-            for k, lo, chunk in members:
+            for k, lo, chunk in members:   # a chunk = one sampling() batch of complex k: steps, write-back, whole-list pass
+                a0, a1 = atom_ptr[j], atom_ptr[j + len(chunk)]
+                if visualization_list is not None:
+                    _visualise_steps(visualization_list[k], lists[k], lo, step_host[:, a0:a1],
+                                     [(atom_ptr[j + i] - a0, atom_ptr[j + i + 1] - a0) for i in range(len(chunk))])
+                if return_full_trajectory:   # the poses of one complex have the same number of atoms
+                    both = torch.cat([pos0[a0:a1].to(step_pos.device, torch.float32)[None], step_pos[:, a0:a1]], 0)
+                    trajectory[k].append(both.reshape(inference_steps + 1, len(chunk), n_l[j], 3))
                 for i in range(len(chunk)):
                     lists[k][lo + i]["ligand"].pos = pos_g[j]
                     j += 1
+                if visualization_list is not None:
+                    _visualise_final(visualization_list[k], lists[k])
             if confidence_model is None:
                 continue
             if confidence_data_lists is not None:   # sampling.py:208-227 on the packed confidence graphs
@@ -329,5 +455,8 @@ def sample_complexes(complex_data_lists, model, inference_steps, tr_schedule, ro
             for (k, _, _), n in zip(members, sizes):
                 confidence[k].append(out[row:row + n])
                 row += n
-    return [(dl, None if confidence is None else torch.nan_to_num(torch.cat(confidence[k], dim=0), nan=-1000))
-            for k, dl in enumerate(lists)]
+    out = [(dl, None if confidence is None else torch.nan_to_num(torch.cat(confidence[k], dim=0), nan=-1000))
+           for k, dl in enumerate(lists)]
+    if return_full_trajectory:
+        out = [o + (torch.cat(trajectory[k], 1),) for k, o in enumerate(out)]
+    return out

@@ -281,6 +281,29 @@ int ddmi_modify_conformer(ddmi_model* m, float* lig_pos, const float* tr_update,
  * in place. */
 int ddmi_sample(ddmi_model* m, float* lig_pos, const ddmi_sample_cfg* cfg, ddmi_stream stream);
 
+/* Per-step record of the ddmi_sample loop (not in the reference, whose Python loop has every step's tensors in hand: the
+ * visualisation hook at utils/sampling.py:193-206 and the NaN warning at :117-124 read them).  The kernels of the step loop that
+ * already hold a value store it into row `step` of the caller's arrays as well: no extra launch, no host synchronisation, and
+ * with no record set ddmi_sample enqueues exactly what it does without this entry point (final poses are bit-identical either
+ * way).  The arrays are CALLER-owned device memory that must stay valid until the enqueued steps have run; every array is
+ * optional (NULL = not recorded).  Rows >= inference_steps are not touched.  G = the NaN-guard groups of the batch layout in
+ * force at ddmi_sample (1 without ddmi_set_batch_layout); n_tor = 0 for no_torsion models.
+ * The record applies to the following ddmi_sample calls on the handle (ddmi_forward, ddmi_perturb and ddmi_modify_conformer
+ * record nothing) until it is replaced, switched off with NULL, or cleared by ddmi_set_complex (the shapes change) or by
+ * ddmi_set_batch_layout (G changes, and with it the row length of nan_count): set the record AFTER the layout.
+ * DDMI_ERR_ARG: struct_size mismatch, capacity_steps < 1 -- and, from ddmi_sample before anything is enqueued,
+ * capacity_steps < inference_steps.  DDMI_ERR_STATE: no complex set. */
+typedef struct ddmi_sample_record {
+  uint32_t struct_size;    /* sizeof(ddmi_sample_record) the caller was built against                                       */
+  int32_t capacity_steps;  /* rows available in every non-NULL array; must be >= inference_steps of the ddmi_sample call    */
+  float* pos;              /* device [capacity_steps, n_lig, 3]: ligand positions AFTER the update of step k, or NULL       */
+  float* tr;               /* device [capacity_steps, B, 3]: tr score of step k after the NaN guard, before the update      */
+  float* rot;              /* device [capacity_steps, B, 3]                                                                 */
+  float* tor;              /* device [capacity_steps, n_tor]; ignored (may be NULL) when the batch has no torsions          */
+  int32_t* nan_count;      /* device [capacity_steps, G]: poses of NaN-guard group g whose mean tr score was NaN at step k  */
+} ddmi_sample_record;
+int ddmi_set_sample_record(ddmi_model* m, const ddmi_sample_record* r); /* NULL switches recording off */
+
 /* One step of the score -> perturbation arithmetic of sampling() -- utils/sampling.py:117-186 -- on caller-owned score
  * arrays, in place: the NaN guard (:117-131: if any pose's mean translation score is NaN, NaN -> 0.01 * nanmean|x|,
  * +-inf -> +-that value, per score tensor) followed by  g^2 dt (lambda + T psi / 2) * score + g sqrt(dt (1 + psi)) * z
