@@ -61,6 +61,11 @@ static void alloc_messages(Model& m, bool copies, int R1) {
       c.rg_aa_all = m.cpool.upload(r9);
       std::vector<ReduceGroup> r3(r9.begin(), r9.begin() + 3);
       c.rg_aa_lig = m.cpool.upload(r3);
+      std::vector<ReduceGroup> r9c = r9;   // per-step crop: the four static relations through their compacted target offsets
+      r9c[3].toff = c.toff2; r9c[5].toff = c.se_ra.toff2; r9c[6].toff = c.se_aa.toff2; r9c[8].toff = c.se_ar.toff2;
+      c.rg_aa_all_crop = m.cpool.upload(r9c);
+      std::vector<ReduceGroup> rec = {r9c[3], r9c[8], r9c[6], r9c[5]};   // the embedding layers' groups [rr, ar, aa, ra]
+      c.rg_emb_crop = m.cpool.upload(rec);
     }
   }
 }
@@ -148,8 +153,12 @@ static void receptor_constants(Model& m, const ddmi_complex& cc, const std::vect
     // aa_model.py:296-318: embedding layers over the sigma-free residue + atom graph, groups [rr, ar, aa, ra]; run in the
     // full node numbering (ligand rows unused) so that the interaction-layer CSRs serve unchanged
     const int aB = nL + nR, nA = c.nA;
-    float* ea = dalloc<float>(m, nullptr, {N, XS}, true);
-    float* eb = dalloc<float>(m, nullptr, {N, XS}, true);
+    float* ea = c.emb_a = dalloc<float>(m, nullptr, {N, XS}, true);
+    float* eb = c.emb_b = dalloc<float>(m, nullptr, {N, XS}, true);
+    // (kept for a per-step crop, which re-embeds the cropped graph from the encoder rows: forward)
+    c.rec_node_enc = dalloc<float>(m, nullptr, {nR, XS}, true); c.atom_node_enc = dalloc<float>(m, nullptr, {nA, XS}, true);
+    DDMI_CHECK_HIP(hipMemcpyAsync(c.rec_node_enc, c.rec_node_base, (size_t)nR * XS * 4, hipMemcpyDeviceToDevice, s));
+    DDMI_CHECK_HIP(hipMemcpyAsync(c.atom_node_enc, c.atom_node_base, (size_t)nA * XS * 4, hipMemcpyDeviceToDevice, s));
     DDMI_CHECK_HIP(hipMemcpyAsync(ea + (size_t)nL * XS, c.rec_node_base, (size_t)nR * XS * 4, hipMemcpyDeviceToDevice, s));
     DDMI_CHECK_HIP(hipMemcpyAsync(ea + (size_t)aB * XS, c.atom_node_base, (size_t)nA * XS * 4, hipMemcpyDeviceToDevice, s));
     RunGroup e_rr{nL, nR, nL, nR, c.rr_goff, c.rr_tgt, c.rr_tslot, c.rr_arow, c.rec_edge_base, c.Err, nullptr, nullptr, nullptr,
@@ -214,7 +223,6 @@ void set_complex(Model& m, const ddmi_complex& cc, hipStream_t s) {
   if (cfg.all_atoms) {
     DDMI_REQUIRE(cc.n_atom > 0 && cc.atom_ptr && cc.atom_x && cc.atom_pos && cc.atom_edge_index && cc.atom_rec_edge_index,
                  DDMI_ERR_ARG, "all_atoms model: atom arrays missing in ddmi_complex");
-    DDMI_REQUIRE(m.crop_cutoff <= 0.0, DDMI_ERR_ARG, "crop_beyond is not implemented for the all-atom model (aa_model.py:365-367)");
     c.nA = cc.n_atom; c.Eaa = cc.n_atom_edges; c.Ear = cc.n_atom_rec_edges;
     c.N = c.nL + c.nR + c.nA;
   }
@@ -247,7 +255,7 @@ void set_complex(Model& m, const ddmi_complex& cc, hipStream_t s) {
   c.Ell_cap = c.Eb + c.lig_cap * c.nL;
   // ---- all_atoms: atom batches and the three static atom relations (gather-ordered CSR + target slots)
   std::vector<int> atom_ptr_h, atom_batch, aa_tl, aa_gl, ar_atom, ar_rec, aa_batch_h, ar_batch_h;
-  struct HostEdges { std::vector<int> goff, toff, arow, tgt, tslot; };
+  struct HostEdges { std::vector<int> goff, toff, arow, tgt, tslot, tlist, gnode; };
   auto build_static = [&](const std::vector<int>& tl, const std::vector<int>& gl, int n_t, int n_g, int tgt_base) {
     HostEdges h;
     const int E = (int)tl.size();
@@ -261,7 +269,12 @@ void set_complex(Model& m, const ddmi_complex& cc, hipStream_t s) {
     h.arow.resize(E); h.tgt.resize(E); h.tslot.resize(E);
     std::vector<int> cur(h.goff.begin(), h.goff.end() - 1), tcur(h.toff.begin(), h.toff.end() - 1);
     for (int k = 0; k < E; ++k) h.arow[cur[gl[k]]++] = k;
-    for (int e = 0; e < E; ++e) { const int k = h.arow[e]; h.tgt[e] = tgt_base + tl[k]; h.tslot[e] = tcur[tl[k]]++; }
+    h.tlist.resize(E); h.gnode.resize(E);
+    for (int e = 0; e < E; ++e) {
+      const int k = h.arow[e];
+      h.tgt[e] = tgt_base + tl[k]; h.tslot[e] = tcur[tl[k]]++;
+      h.tlist[h.tslot[e]] = e; h.gnode[e] = gl[k];
+    }
     return h;
   };
   HostEdges h_aa, h_ar, h_ra;
@@ -286,6 +299,9 @@ void set_complex(Model& m, const ddmi_complex& cc, hipStream_t s) {
     aa_batch_h.resize(c.Eaa); ar_batch_h.resize(c.Ear);
     for (int k = 0; k < c.Eaa; ++k) aa_batch_h[k] = atom_batch[aa_tl[k]];     // atom.batch[edge_index[0]] (aa_model.py:332)
     for (int k = 0; k < c.Ear; ++k) ar_batch_h[k] = atom_batch[ar_atom[k]];   // (aa_model.py:335)
+    // the reference's crop rewrites atom_rec_contact as arange(kept atoms) (utils/utils.py:395-399): defined when edge k belongs to atom k
+    c.ar_arange = c.Ear == c.nA;
+    for (int k = 0; k < c.Ear && c.ar_arange; ++k) c.ar_arange = ar_atom[k] == k;
   }
   // bonds: ranks inside the gather (edge_index[1]) and target (edge_index[0]) lists
   std::vector<int> bsrc(c.Eb), bdst(c.Eb), bgr(c.Eb), btr(c.Eb), bg(c.nL, 0), bt(c.nL, 0);
@@ -352,14 +368,23 @@ void set_complex(Model& m, const ddmi_complex& cc, hipStream_t s) {
     DDMI_CHECK_HIP(hipMemcpy(c.atom_x, cc.atom_x, (size_t)c.nA * 4 * 4, hipMemcpyDeviceToDevice));
     c.atom_pos = dalloc<float>(m, nullptr, {c.nA * 3});
     DDMI_CHECK_HIP(hipMemcpy(c.atom_pos, cc.atom_pos, (size_t)c.nA * 12, hipMemcpyDeviceToDevice));
-    auto up_edges = [&](const HostEdges& h, const char* name) {
+    auto up_edges = [&](const HostEdges& h, const char* name, const char* crop_name) {
       Cx::StaticEdges e;
       e.E = (int)h.arow.size();
+      const int n_g = (int)h.goff.size() - 1, n_t = (int)h.toff.size() - 1;
       e.goff = dup(m, name, h.goff); e.toff = dup(m, nullptr, h.toff); e.arow = dup(m, nullptr, h.arow);
       e.tgt = dup(m, nullptr, h.tgt); e.tslot = dup(m, nullptr, h.tslot);
+      e.tlist = dup(m, nullptr, h.tlist); e.gnode = dup(m, nullptr, h.gnode);
+      e.cnt_g = dalloc<int>(m, nullptr, {n_g}); e.cnt_t = dalloc<int>(m, nullptr, {n_t});
+      e.goff2 = dalloc<int>(m, crop_name, {n_g + 1}); e.toff2 = dalloc<int>(m, nullptr, {n_t + 1});
+      e.tslot_tmp = dalloc<int>(m, nullptr, {e.E}); e.tgt2 = dalloc<int>(m, nullptr, {e.E});
+      e.tslot2 = dalloc<int>(m, nullptr, {e.E}); e.arow2 = dalloc<int>(m, nullptr, {e.E});
       return e;
     };
-    c.se_aa = up_edges(h_aa, "aa_goff"); c.se_ar = up_edges(h_ar, "ar_goff"); c.se_ra = up_edges(h_ra, "ra_goff");
+    c.se_aa = up_edges(h_aa, "aa_goff", "aa_goff_crop"); c.se_ar = up_edges(h_ar, "ar_goff", "ar_goff_crop");
+    c.se_ra = up_edges(h_ra, "ra_goff", "ra_goff_crop");
+    c.keep_atom = dalloc<int>(m, "crop_keep_atom", {c.nA});
+    if (c.ar_arange) c.atom_res = dup(m, nullptr, ar_rec);
     c.aa_batch = dup(m, nullptr, aa_batch_h); c.ar_batch = dup(m, nullptr, ar_batch_h);
     int* aa_src = dup(m, nullptr, aa_tl); int* aa_dst = dup(m, nullptr, aa_gl);
     int* ar_src = dup(m, nullptr, ar_atom); int* ar_dst = dup(m, nullptr, ar_rec);

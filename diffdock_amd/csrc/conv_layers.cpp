@@ -239,7 +239,8 @@ LayerPlan plan_layer(const Model& m, const ConvW& L, const RunGroup* groups, int
   const bool layer_buffers = all_mm && n <= 9 && c.Pg[0];
   if (overlapped) P.runner = LayerPlan::overlapped;
   else if (r.grouped == 2 && layer_buffers && c.Hbg[0] && n >= 2 && all_lists && !L.fgran_generic && L.maxd <= 3 && m.cfg.sh_lmax <= 1 &&
-           L.n_fgran > 0 && m.cfg.edge_product == 0 && !(m.timing && m.timing_level >= 2))   // (per-group timing rows need per-group launches)
+           L.n_fgran > 0 && m.cfg.edge_product == 0 && !(m.timing && m.timing_level >= 2) &&   // (per-group timing rows need per-group launches)
+           !(m.cfg.all_atoms && m.crop_cutoff > 0.0))   // (an all-atom crop takes the per-group path)
     P.runner = LayerPlan::grouped;
   const bool is_grouped = P.runner == LayerPlan::grouped;
   P.mm_all = is_grouped || (!overlapped && (pq_mode != 0 || (r.fc1_batch && P.small_layer)) && layer_buffers);

@@ -66,11 +66,21 @@ struct Model::Cx {
   int nA = 0, maxNa = 0, Eaa = 0, Ear = 0, Ela_cap = 0;
   int *atom_batch = nullptr, *atom_ptr = nullptr, *atom_x = nullptr;
   float* atom_pos = nullptr;
-  struct StaticEdges { int E = 0; int *goff = nullptr, *toff = nullptr, *arow = nullptr, *tgt = nullptr, *tslot = nullptr; };
+  // a static atom relation: gather-order CSR (goff, tgt, tslot, arow), target order (toff; tlist = gather-order id of a slot, gnode =
+  // gather node of an edge) and its per-step compaction under a crop (launch_rel_filter; the *2 arrays, like goff2.. of rec-rec)
+  struct StaticEdges { int E = 0; int *goff = nullptr, *toff = nullptr, *arow = nullptr, *tgt = nullptr, *tslot = nullptr;
+                       int *tlist = nullptr, *gnode = nullptr;
+                       int *cnt_g = nullptr, *cnt_t = nullptr, *goff2 = nullptr, *toff2 = nullptr, *tslot_tmp = nullptr, *tgt2 = nullptr,
+                           *tslot2 = nullptr, *arow2 = nullptr; };
   StaticEdges se_aa, se_ar, se_ra;   // atom<-atom; atom<-rec (group "ar"); rec<-atom (the flipped group)
+  // all-atom crop: atom mask = the mask of the atom's residue (atom_res = row 1 of atom_rec_edge_index)
+  int *keep_atom = nullptr, *atom_res = nullptr;
+  bool ar_arange = false;   // edge k of atom_rec_edge_index belongs to atom k: what the reference's all-atom crop is defined for
+  ReduceGroup *rg_aa_all_crop = nullptr, *rg_emb_crop = nullptr;
   int *aa_batch = nullptr, *ar_batch = nullptr;
   float *aa_dist = nullptr, *aa_nvec = nullptr, *aa_ew = nullptr, *atom_edge_base = nullptr;
   float *ar_dist = nullptr, *ar_nvec = nullptr, *ar_edge_base = nullptr, *atom_node_base = nullptr;
+  float *atom_node_enc = nullptr, *emb_a = nullptr, *emb_b = nullptr;   // embedding layers: atom encoder rows before them, the two [N] tables they run in
   int *la_pairrank = nullptr, *la_cnt_l = nullptr, *la_cnt_a = nullptr, *la_offs_l = nullptr, *la_offs_a = nullptr;
   int *la1_tgt = nullptr, *la1_tslot = nullptr, *la3_tgt = nullptr, *la3_tslot = nullptr, *la_pbatch = nullptr;
   float *la_dist = nullptr, *la_nvec = nullptr, *la_ew = nullptr, *la_ea = nullptr, *la_gvec = nullptr;

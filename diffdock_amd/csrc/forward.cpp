@@ -248,16 +248,25 @@ static void time_terms(Model& m, const float* t_tr, bool conf, hipStream_t s) {
   gemm(c.hidB, ns, m.rec_sigma.W3, ns, m.rec_sigma.b3, c.rec_sig, ns, B, ns, ns, 0, s);
 }
 
-// ---- all-atom model (aa_model.py:364-436): atom rows, ligand<->atom radius graph, nine edge groups
+// a static atom relation as an edge group reads it: the per-complex CSR, or its compaction of this forward under a crop
+struct Rel { const int *goff, *tgt, *tslot, *arow; };
+static Rel rel_of(const Cx::StaticEdges& e, bool crop) {
+  return crop ? Rel{e.goff2, e.tgt2, e.tslot2, e.arow2} : Rel{e.goff, e.tgt, e.tslot, e.arow};
+}
+
+// ---- all-atom model (aa_model.py:364-436): atom rows (atom_rows: their embedding without the sigma term), ligand<->atom radius
+// graph, nine edge groups.  crop: the atoms of the cropped residues are gone too (utils/utils.py:393-411) -- masked out of the radius
+// graph, the static atom relations read through their compaction (forward); g_rr comes in cropped already.
 static void run_aa_layers(Model& m, const float* lig_pos, const RunGroup& g_ll, const RunGroup& g_lr, const RunGroup& g_rr,
-                          const RunGroup& g_rl, int& xi, std::unique_ptr<PhaseTimer>& t_phase, hipStream_t s) {
+                          const RunGroup& g_rl, bool crop, const float* atom_rows, int& xi, std::unique_ptr<PhaseTimer>& t_phase,
+                          hipStream_t s) {
   Cx& c = *m.cx;
   const ddmi_config& cfg = m.cfg;
   const int ns = m.ns, sd = m.sd, B = c.B, nL = c.nL, nR = c.nR, Lc = (int)m.conv_layers.size();
   const int nA = c.nA, aB = nL + nR;
-  launch_add_rowvec(c.X[xi] + (size_t)aB * XS, XS, c.atom_node_base, XS, c.rec_sig, ns, c.atom_batch, nA, c.rec_base_dim, ns, s);
+  launch_add_rowvec(c.X[xi] + (size_t)aB * XS, XS, atom_rows, XS, c.rec_sig, ns, c.atom_batch, nA, c.rec_base_dim, ns, s);
   launch_cross_count(lig_pos, c.atom_pos, c.lig_batch, c.atom_batch, c.lig_ptr, c.atom_ptr, nL, nA, c.maxNa, nullptr,
-                     cfg.lig_max_radius, nullptr, c.la_pairrank, c.la_cnt_l, c.la_cnt_a, s);
+                     cfg.lig_max_radius, crop ? c.keep_atom : nullptr, c.la_pairrank, c.la_cnt_l, c.la_cnt_a, s);
   launch_exclusive_scan2(c.la_cnt_l, c.la_offs_l, nL, c.la_cnt_a, c.la_offs_a, nA, s);
   launch_cross_fill(lig_pos, c.atom_pos, c.atom_batch, c.lig_ptr, c.atom_ptr, nL, nA, c.maxNa, c.la_pairrank, c.la_offs_l,
                     c.la_offs_a, nullptr, cfg.lig_max_radius, cfg.smooth_edges, c.la1_tgt, c.la1_tslot, c.la3_tgt, c.la3_tslot,
@@ -272,21 +281,22 @@ static void run_aa_layers(Model& m, const float* lig_pos, const RunGroup& g_ll, 
   a_ll.msg = c.msg_aa[0]; a_lr.msg = c.msg_aa[1]; a_rr.msg = c.msg_aa[3]; a_rl.msg = c.msg_aa[4];
   RunGroup a_la{aB, nA, 0, nL, c.la_offs_a, c.la1_tgt, c.la1_tslot, c.la1_tslot, c.la_ea, c.Ela_cap, c.la_offs_l + nL, nullptr,
                 nullptr, c.la_nvec, c.la_ew, 1.f, c.msg_aa[2]};
-  RunGroup a_ra{aB, nA, nL, nR, c.se_ra.goff, c.se_ra.tgt, c.se_ra.tslot, c.se_ra.arow, c.ar_edge_base, c.Ear, nullptr, c.rec_sig,
+  const Rel ra = rel_of(c.se_ra, crop), aa = rel_of(c.se_aa, crop), ar = rel_of(c.se_ar, crop);
+  RunGroup a_ra{aB, nA, nL, nR, ra.goff, ra.tgt, ra.tslot, ra.arow, c.ar_edge_base, c.Ear, nullptr, c.rec_sig,
                 c.ar_batch, c.ar_nvec, nullptr, 1.f, c.msg_aa[5]};
-  RunGroup a_aa{aB, nA, aB, nA, c.se_aa.goff, c.se_aa.tgt, c.se_aa.tslot, c.se_aa.arow, c.atom_edge_base, c.Eaa, nullptr, c.rec_sig,
+  RunGroup a_aa{aB, nA, aB, nA, aa.goff, aa.tgt, aa.tslot, aa.arow, c.atom_edge_base, c.Eaa, nullptr, c.rec_sig,
                 c.aa_batch, c.aa_nvec, c.aa_ew, 1.f, c.msg_aa[6]};
   RunGroup a_al{0, nL, aB, nA, c.la_offs_l, c.la3_tgt, c.la3_tslot, nullptr, c.la_ea, c.Ela_cap, c.la_offs_l + nL, nullptr,
                 nullptr, c.la_nvec, c.la_ew, 1.f, c.msg_aa[7]};
-  RunGroup a_ar{nL, nR, aB, nA, c.se_ar.goff, c.se_ar.tgt, c.se_ar.tslot, c.se_ar.arow, c.ar_edge_base, c.Ear, nullptr, c.rec_sig,
+  RunGroup a_ar{nL, nR, aB, nA, ar.goff, ar.tgt, ar.tslot, ar.arow, c.ar_edge_base, c.Ear, nullptr, c.rec_sig,
                 c.ar_batch, c.ar_nvec, nullptr, 1.f, c.msg_aa[8]};
   a_la.vn = 4; a_ra.vn = 5; a_aa.vn = 6; a_al.vn = 7; a_al.load = true; a_ar.vn = 8;
-  a_ra.static_topo = a_aa.static_topo = a_ar.static_topo = true;   // static atom relations (set_complex)
+  a_ra.static_topo = a_aa.static_topo = a_ar.static_topo = !crop;   // static atom relations (set_complex) unless cropped per step
   t_phase.reset();
   for (int l = 0; l < Lc; ++l, ++xi) {
     if (l < Lc - 1)
-      run_conv(m, m.conv_layers[l], {a_ll, a_lr, a_la, a_rr, a_rl, a_ra, a_aa, a_al, a_ar}, c.rg_aa_all, 9, c.X[xi], c.X[xi + 1], 0,
-               c.N, s);
+      run_conv(m, m.conv_layers[l], {a_ll, a_lr, a_la, a_rr, a_rl, a_ra, a_aa, a_al, a_ar}, crop ? c.rg_aa_all_crop : c.rg_aa_all, 9,
+               c.X[xi], c.X[xi + 1], 0, c.N, s);
     else run_conv(m, m.conv_layers[l], {a_ll, a_lr, a_la}, c.rg_aa_lig, 3, c.X[xi], c.X[xi + 1], 0, nL, s);
   }
 }
@@ -339,7 +349,9 @@ void forward(Model& m, const float* lig_pos, const float* t_tr, const float* t_r
   // MLP -- which needs the per-graph time term -- behind an event; the ligand node encoder and the receptor rows of the first table
   // (time terms only) follow it there, so the main stream goes from the time terms straight to the ligand graph.
   const bool crop = m.crop_cutoff > 0.0;
-  DDMI_REQUIRE(!(crop && cfg.all_atoms), DDMI_ERR_ARG, "crop_beyond is not implemented for the all-atom model (aa_model.py:365-367)");
+  DDMI_REQUIRE(!(crop && cfg.all_atoms) || c.ar_arange, DDMI_ERR_ARG,
+               "crop_beyond of an all-atom complex needs one atom_rec_edge_index column per atom, column k for atom k (n_atom_rec_edges == "
+               "n_atom, row 0 == 0..n_atom-1): the reference rewrites the relation as arange(kept atoms) (utils/utils.py:395-399)");
   const float* cut_dev = cfg.dynamic_max_cross ? c.cutoff : nullptr;
   auto cross_pairs = [&](hipStream_t cs, const int* keep_) {
     if (cfg.dynamic_max_cross)   // cutoff_b = 3 * tr_sigma_b + 20 (cg_model.py:321-322)
@@ -389,17 +401,57 @@ void forward(Model& m, const float* lig_pos, const float* t_tr, const float* t_r
   int xi = 0;
   for (size_t i = 0; i < m.lig_emb_layers.size(); ++i, ++xi)
     run_conv(m, m.lig_emb_layers[i], {g_ll}, c.rg_ll, 1, c.X[xi], c.X[xi + 1], 0, nL, s);
-  // ---- per-step receptor crop (utils/sampling.py:104-109): residue mask + re-compacted contact graph
+  // ---- per-step receptor crop (utils/sampling.py:104-109, utils/utils.py:388-413): residue mask (all_atoms: + the mask of their
+  // atoms) and the static relations re-compacted under the masks -- the contact graph; all_atoms: atom-atom, atom<-rec, rec<-atom
   const int* keep = nullptr;
   if (crop) {
     const double cd = m.crop_cutoff;
-    launch_crop_mask(lig_pos, c.rec_pos, c.rec_batch, c.lig_ptr, nR, (float)(cd * cd), c.keep, s);
-    launch_rr_filter(c.keep, c.rr_goff, c.rr_tgt, c.rr_arow, c.rr_toff, c.rr_tlist, c.rr_gnode, nL, nR, c.cnt_g2, c.cnt_t2,
-                     c.goff2, c.toff2, c.tslot_tmp, c.tgt2, c.tslot2, c.arow2, s);
+    const int aB = nL + nR, nA = c.nA;
+    {
+      PhaseTimer t(m, "k_crop_mask", s);
+      launch_crop_mask(lig_pos, c.rec_pos, c.rec_batch, c.lig_ptr, nR, (float)(cd * cd), c.keep, s);
+      if (cfg.all_atoms) launch_crop_atom_mask(c.keep, c.atom_res, nA, c.keep_atom, s);
+    }
+    RelFilterArgs fa;
+    fa.r[fa.n++] = RelFilter{c.keep, c.keep, nR, nR, nL, c.rr_goff, c.rr_tgt, c.rr_arow, c.rr_toff, c.rr_tlist, c.rr_gnode,
+                             c.cnt_g2, c.cnt_t2, c.goff2, c.toff2, c.tslot_tmp, c.tgt2, c.tslot2, c.arow2};
+    auto add = [&](const Cx::StaticEdges& e, const int* gkeep, int gn, const int* tkeep, int tn, int tbase) {
+      fa.r[fa.n++] = RelFilter{gkeep, tkeep, gn, tn, tbase, e.goff, e.tgt, e.arow, e.toff, e.tlist, e.gnode,
+                               e.cnt_g, e.cnt_t, e.goff2, e.toff2, e.tslot_tmp, e.tgt2, e.tslot2, e.arow2};
+    };
+    if (cfg.all_atoms) {
+      add(c.se_aa, c.keep_atom, nA, c.keep_atom, nA, aB);
+      add(c.se_ar, c.keep, nR, c.keep_atom, nA, aB);
+      add(c.se_ra, c.keep_atom, nA, c.keep, nR, nL);
+    }
+    PhaseTimer t(m, "k_rel_filter", s);
+    launch_rel_filter(fa, s);
     keep = c.keep;
   }
   // receptor rows of the current table: cached embedding + sigma term on the scalars (cg_model.py:298-301)
-  if (crop && !m.rec_emb_layers.empty()) {
+  const float* atom_rows = c.atom_node_base;
+  if (crop && !m.rec_emb_layers.empty() && cfg.all_atoms) {
+    // aa_model.py:296-318 on the CROPPED residue + atom graph (the reference re-embeds it every step, see below): groups
+    // [rr, ar, aa, ra] through the compacted relations, from the encoder rows, in the two tables set_complex embedded in
+    const int aB = nL + nR, nA = c.nA;
+    DDMI_CHECK_HIP(hipMemcpyAsync(c.emb_a + (size_t)nL * XS, c.rec_node_enc, (size_t)nR * XS * 4, hipMemcpyDeviceToDevice, s));
+    DDMI_CHECK_HIP(hipMemcpyAsync(c.emb_a + (size_t)aB * XS, c.atom_node_enc, (size_t)nA * XS * 4, hipMemcpyDeviceToDevice, s));
+    const Rel ra = rel_of(c.se_ra, true), aa = rel_of(c.se_aa, true), ar = rel_of(c.se_ar, true);
+    RunGroup e_rr{nL, nR, nL, nR, c.goff2, c.tgt2, c.tslot2, c.arow2, c.rec_edge_base, c.Err, nullptr, nullptr, nullptr,
+                  c.rr_nvec, c.rr_ew, 1.f, c.msg_aa[3]};
+    RunGroup e_ar{nL, nR, aB, nA, ar.goff, ar.tgt, ar.tslot, ar.arow, c.ar_edge_base, c.Ear, nullptr, nullptr, nullptr,
+                  c.ar_nvec, nullptr, 1.f, c.msg_aa[8]};
+    RunGroup e_aa{aB, nA, aB, nA, aa.goff, aa.tgt, aa.tslot, aa.arow, c.atom_edge_base, c.Eaa, nullptr, nullptr, nullptr,
+                  c.aa_nvec, c.aa_ew, 1.f, c.msg_aa[6]};
+    RunGroup e_ra{aB, nA, nL, nR, ra.goff, ra.tgt, ra.tslot, ra.arow, c.ar_edge_base, c.Ear, nullptr, nullptr, nullptr,
+                  c.ar_nvec, nullptr, 1.f, c.msg_aa[5]};
+    e_rr.vn = 1; e_ar.vn = 8; e_aa.vn = 6; e_ra.vn = 5;
+    float *xin = c.emb_a, *xout = c.emb_b;
+    for (size_t i = 0; i < m.rec_emb_layers.size(); ++i, std::swap(xin, xout))
+      run_conv(m, m.rec_emb_layers[i], {e_rr, e_ar, e_aa, e_ra}, c.rg_emb_crop, 4, xin, xout, nL, nR + nA, s);
+    atom_rows = xin + (size_t)aB * XS;
+    launch_add_rowvec(c.X[xi] + (size_t)nL * XS, XS, xin + (size_t)nL * XS, XS, c.rec_sig, ns, c.rec_batch, nR, c.rec_base_dim, ns, s);
+  } else if (crop && !m.rec_emb_layers.empty()) {
     // the reference re-embeds the CROPPED receptor every step (the cache lives on the discarded deep copy)
     launch_add_rowvec(c.X[0] + (size_t)nL * XS, XS, c.rec_node_enc, XS, nullptr, 0, nullptr, nR, ns, 0, s);
     RunGroup g_rr0{nL, nR, nL, nR, c.goff2, c.tgt2, c.tslot2, c.arow2, c.rec_edge_base, c.Err, nullptr, nullptr,
@@ -424,7 +476,7 @@ void forward(Model& m, const float* lig_pos, const float* t_tr, const float* t_r
                 nullptr, c.pnvec, c.pew, -1.f, c.msg[3]};
   g_lr.vn = 0; g_rr.vn = 1; g_rl.vn = 3; g_rl.load = true;
   g_rr.static_topo = !crop;   // the contact graph of an uncropped receptor is a per-complex constant: its lists and per-edge rows are built once
-  if (cfg.all_atoms) run_aa_layers(m, lig_pos, g_ll, g_lr, g_rr, g_rl, xi, t_phase, s);
+  if (cfg.all_atoms) run_aa_layers(m, lig_pos, g_ll, g_lr, g_rr, g_rl, crop, atom_rows, xi, t_phase, s);
   else {
     t_phase.reset();
     run_cg_layers(m, g_ll, g_lr, g_rr, g_rl, crop, xi, s);

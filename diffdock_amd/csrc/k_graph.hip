@@ -8,6 +8,8 @@
 // Ranks come from counting scans (no atomics), so layouts -- and therefore fp32 summation
 // orders -- are reproducible run to run.  Neighbour caps keep the first `cap` hits in ascending
 // index order (torch_cluster's CUDA kernel behaviour).
+#include <algorithm>
+
 #include "kernels.h"
 
 namespace ddmi {
@@ -336,52 +338,90 @@ void launch_rows_differ(const float* a, int lda, const float* b, int ldb, int n_
   DDMI_CHECK_HIP(hipGetLastError());
 }
 
-// static CSRs: gather order (goff, src = tgt - nL, dst = the gather node) and target order (toff, tlist = gather-order id)
-__global__ void k_rr_filter_count(const int* __restrict__ keep, const int* __restrict__ goff, const int* __restrict__ tgt,
-                                  const int* __restrict__ toff, const int* __restrict__ tlist,
-                                  const int* __restrict__ gnode, int nL, int nR, int* __restrict__ cnt_g,
-                                  int* __restrict__ cnt_t) {
+// all_atoms: an atom survives iff its residue does (utils/utils.py:395-396; res_of = row 1 of atom_rec_edge_index)
+__global__ void k_crop_atom_mask(const int* __restrict__ keep, const int* __restrict__ res_of, int nA, int* __restrict__ keep_atom) {
+  const int a = blockIdx.x * blockDim.x + threadIdx.x;
+  if (a < nA) keep_atom[a] = keep[res_of[a]];
+}
+void launch_crop_atom_mask(const int* keep, const int* res_of, int nA, int* keep_atom, hipStream_t s) {
+  if (nA <= 0) return;
+  hipLaunchKernelGGL(k_crop_atom_mask, dim3(cdiv(nA, 64)), dim3(64), 0, s, keep, res_of, nA, keep_atom);
+  DDMI_CHECK_HIP(hipGetLastError());
+}
+
+// Re-compaction of static relations under the masks of their two ends (rec-rec; all_atoms: atom-atom, atom<-rec, rec<-atom): an edge
+// survives iff its gather node and its target node do, and the survivors keep their order in both CSRs.  Static side: gather order
+// (goff, tgt = tbase + target, arow) and target order (toff, tlist = gather-order id of a slot, gnode = gather node of an edge).
+// Three phases -- count, [scan,] slots, fill -- each ONE launch over the relations of the descriptor array (blockIdx.y): a thread
+// per node, which serves as gather node and as target node of its relation (degrees are bounded by the neighbour caps).
+__global__ void k_rel_filter_count(RelFilterArgs A) {
+  const RelFilter& r = A.r[blockIdx.y];
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
-  if (n >= nR) return;
-  int cg = 0, ct = 0;
-  if (keep[n]) {
-    for (int e = goff[n]; e < goff[n + 1]; ++e) cg += keep[tgt[e] - nL];              // gather node n, target tgt[e]
-    for (int ts = toff[n]; ts < toff[n + 1]; ++ts) ct += keep[gnode[tlist[ts]]];      // target node n, gather gnode[e]
+  if (n < r.gn) {
+    int cg = 0;
+    if (r.gkeep[n]) for (int e = r.goff[n]; e < r.goff[n + 1]; ++e) cg += r.tkeep[r.tgt[e] - r.tbase];
+    r.cnt_g[n] = cg;
   }
-  cnt_g[n] = cg;
-  cnt_t[n] = ct;
-}
-__global__ void k_rr_filter_tslot(const int* __restrict__ keep, const int* __restrict__ toff, const int* __restrict__ tlist,
-                                  const int* __restrict__ gnode, const int* __restrict__ toff2, int nR,
-                                  int* __restrict__ tslot_tmp) {
-  const int n = blockIdx.x * blockDim.x + threadIdx.x;
-  if (n >= nR || !keep[n]) return;
-  int r = toff2[n];
-  for (int ts = toff[n]; ts < toff[n + 1]; ++ts) {
-    const int e = tlist[ts];
-    if (keep[gnode[e]]) tslot_tmp[e] = r++;
+  if (n < r.tn) {
+    int ct = 0;
+    if (r.tkeep[n]) for (int ts = r.toff[n]; ts < r.toff[n + 1]; ++ts) ct += r.gkeep[r.gnode[r.tlist[ts]]];
+    r.cnt_t[n] = ct;
   }
 }
-__global__ void k_rr_filter_fill(const int* __restrict__ keep, const int* __restrict__ goff, const int* __restrict__ tgt,
-                                 const int* __restrict__ arow, const int* __restrict__ tslot_tmp,
-                                 const int* __restrict__ goff2, int nL, int nR, int* __restrict__ tgt2,
-                                 int* __restrict__ tslot2, int* __restrict__ arow2) {
+// target node n: new slots of its surviving edges, in the old slot order
+__global__ void k_rel_filter_tslot(RelFilterArgs A) {
+  const RelFilter& r = A.r[blockIdx.y];
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
-  if (n >= nR || !keep[n]) return;
-  int q = goff2[n];
-  for (int e = goff[n]; e < goff[n + 1]; ++e)
-    if (keep[tgt[e] - nL]) { tgt2[q] = tgt[e]; tslot2[q] = tslot_tmp[e]; arow2[q] = arow[e]; ++q; }
+  if (n >= r.tn || !r.tkeep[n]) return;
+  int q = r.toff2[n];
+  for (int ts = r.toff[n]; ts < r.toff[n + 1]; ++ts) {
+    const int e = r.tlist[ts];
+    if (r.gkeep[r.gnode[e]]) r.tslot_tmp[e] = q++;
+  }
 }
-void launch_rr_filter(const int* keep, const int* goff, const int* tgt, const int* arow, const int* toff, const int* tlist,
-                      const int* gnode, int nL, int nR, int* cnt_g, int* cnt_t, int* goff2, int* toff2, int* tslot_tmp,
-                      int* tgt2, int* tslot2, int* arow2, hipStream_t s) {
-  if (nR <= 0) return;
-  const dim3 grid(cdiv(nR, 64)), block(64);
-  hipLaunchKernelGGL(k_rr_filter_count, grid, block, 0, s, keep, goff, tgt, toff, tlist, gnode, nL, nR, cnt_g, cnt_t);
-  launch_exclusive_scan(cnt_g, goff2, nR, s);
-  launch_exclusive_scan(cnt_t, toff2, nR, s);
-  hipLaunchKernelGGL(k_rr_filter_tslot, grid, block, 0, s, keep, toff, tlist, gnode, toff2, nR, tslot_tmp);
-  hipLaunchKernelGGL(k_rr_filter_fill, grid, block, 0, s, keep, goff, tgt, arow, tslot_tmp, goff2, nL, nR, tgt2, tslot2, arow2);
+// gather node n: its surviving edges, in the old gather order
+__global__ void k_rel_filter_fill(RelFilterArgs A) {
+  const RelFilter& r = A.r[blockIdx.y];
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= r.gn || !r.gkeep[n]) return;
+  int q = r.goff2[n];
+  for (int e = r.goff[n]; e < r.goff[n + 1]; ++e)
+    if (r.tkeep[r.tgt[e] - r.tbase]) { r.tgt2[q] = r.tgt[e]; r.tslot2[q] = r.tslot_tmp[e]; r.arow2[q] = r.arow[e]; ++q; }
+}
+// the 2 n degree scans of the relations in one launch (block = one array)
+__global__ __launch_bounds__(1024) void k_rel_filter_scan(RelFilterArgs A) {
+  __shared__ int part[1024];
+  const RelFilter& r = A.r[blockIdx.x >> 1];
+  const bool tside = blockIdx.x & 1;
+  const int* __restrict__ in = tside ? r.cnt_t : r.cnt_g;
+  int* __restrict__ out = tside ? r.toff2 : r.goff2;
+  const int n = tside ? r.tn : r.gn;
+  const int t = threadIdx.x;
+  const int per = (n + 1023) / 1024;
+  const int lo = min(t * per, n), hi = min(lo + per, n);
+  int s = 0;
+  for (int i = lo; i < hi; ++i) s += in[i];
+  part[t] = s;
+  __syncthreads();
+  for (int off = 1; off < 1024; off <<= 1) {
+    int v = t >= off ? part[t - off] : 0;
+    __syncthreads();
+    part[t] += v;
+    __syncthreads();
+  }
+  int run = part[t] - s;
+  for (int i = lo; i < hi; ++i) { const int v = in[i]; out[i] = run; run += v; }
+  if (t == 1023) out[n] = part[1023];
+}
+void launch_rel_filter(const RelFilterArgs& A, hipStream_t s) {
+  int nmax = 0;
+  for (int i = 0; i < A.n; ++i) nmax = std::max(nmax, std::max(A.r[i].gn, A.r[i].tn));
+  if (A.n <= 0 || nmax <= 0) return;
+  const dim3 grid(cdiv(nmax, 64), A.n), block(64);
+  hipLaunchKernelGGL(k_rel_filter_count, grid, block, 0, s, A);
+  hipLaunchKernelGGL(k_rel_filter_scan, dim3(2 * A.n), dim3(1024), 0, s, A);
+  hipLaunchKernelGGL(k_rel_filter_tslot, grid, block, 0, s, A);
+  hipLaunchKernelGGL(k_rel_filter_fill, grid, block, 0, s, A);
   DDMI_CHECK_HIP(hipGetLastError());
 }
 

@@ -219,9 +219,18 @@ void launch_crop_mask(const float* lpos, const float* rpos, const int* rbatch, c
 // *differ = 1 if any of the rows [n_one, n_one * copies) of a (ld-wide) or b (ldb-wide) differs bitwise from the row of graph 0 at
 // the same local index (rows of graph q = [q * n_one, (q + 1) * n_one)); *differ is left untouched otherwise
 void launch_rows_differ(const float* a, int lda, const float* b, int ldb, int n_one, int copies, int* differ, hipStream_t s);
-void launch_rr_filter(const int* keep, const int* goff, const int* tgt, const int* arow, const int* toff, const int* tlist,
-                      const int* gnode, int nL, int nR, int* cnt_g, int* cnt_t, int* goff2, int* toff2, int* tslot_tmp,
-                      int* tgt2, int* tslot2, int* arow2, hipStream_t s);
+void launch_crop_atom_mask(const int* keep, const int* res_of, int nA, int* keep_atom, hipStream_t s);   // keep_atom[a] = keep[res_of[a]]
+// One static relation under a crop: masks of its gather / target nodes (local ids), the static CSRs in gather order (goff, tgt = tbase +
+// local target, arow) and in target order (toff, tlist, gnode); out: degree counts, compacted offsets and the surviving edges in their
+// old order (tslot_tmp: new slot of every old gather-order edge)
+struct RelFilter {
+  const int *gkeep, *tkeep; int gn, tn, tbase;
+  const int *goff, *tgt, *arow, *toff, *tlist, *gnode;
+  int *cnt_g, *cnt_t, *goff2, *toff2, *tslot_tmp, *tgt2, *tslot2, *arow2;
+};
+constexpr int REL_FILTER_MAX = 4;
+struct RelFilterArgs { int n = 0; RelFilter r[REL_FILTER_MAX]; };
+void launch_rel_filter(const RelFilterArgs& A, hipStream_t s);   // four launches for all relations: count, scans, slots, fill
 void launch_cross_fill(const float* lpos, const float* rpos, const int* rbatch, const int* lptr, const int* rptr, int nL,
                        int nR, int maxNr, const int* pairrank, const int* offs_l, const int* offs_r, const float* cutoff,
                        float const_cutoff, int smooth, int* g1_tgt, int* g1_tslot, int* g3_tgt, int* g3_tslot,

@@ -266,9 +266,20 @@ int ddmi_sidechain_pred(ddmi_model* m, float* out, ddmi_stream stream);
 int ddmi_confidence(ddmi_model* m, const float* lig_pos, const float* t_tr, const float* t_rot, const float* t_tor,
                     float* conf_out, float* atom_conf_out, ddmi_stream stream);
 
-/* crop_beyond(graph, cutoff) -- utils/utils.py:388-413 as applied by sampling() before each model call
- * (utils/sampling.py:104-109): subsequent ddmi_forward calls drop the residues farther than `cutoff` from every
- * ligand atom of their graph, with the contact edges touching them.  cutoff <= 0 switches cropping off. */
+/* crop_beyond(graph, cutoff, all_atoms) -- utils/utils.py:388-413 as applied by sampling() before each model call
+ * (utils/sampling.py:104-109): subsequent ddmi_forward / ddmi_confidence calls drop the residues farther than `cutoff`
+ * from every ligand atom of their graph, with the contact edges touching them.  cutoff <= 0 switches cropping off;
+ * ddmi_sample sets its own cutoff per step (ddmi_sample_cfg.use_crop) and restores this one.
+ * All-atom models: the atoms of a dropped residue go with it (atom a belongs to residue atom_rec_edge_index[1][a]),
+ * atom_contact keeps the edges between kept atoms, the ligand-atom radius graph sees kept atoms only, and embedding layers
+ * (num_prot_emb_layers > 0) are re-run on the cropped residue + atom graph in every call, as in the reference.  The reference
+ * rewrites atom_rec_contact as arange(kept atoms), which is defined only when column k of atom_rec_edge_index belongs to
+ * atom k: n_atom_rec_edges == n_atom and row 0 == 0..n_atom-1 (what the reference's preprocessing writes).  A complex that
+ * does not have this form evaluates without a cutoff as always; with a cutoff set, ddmi_forward / ddmi_confidence /
+ * ddmi_sample return DDMI_ERR_ARG.
+ * Dropped residues and atoms stay rows of the node tables and keep no edges (debug buffers crop_keep [n_rec],
+ * crop_keep_atom [n_atom]: 1 = kept).  A graph that keeps no residue is not refused on the device (the reference would
+ * fail on its empty receptor): its ligand rows are computed without receptor or atom messages -- CG and all-atom alike. */
 int ddmi_set_crop_cutoff(ddmi_model* m, float cutoff);
 
 /* modify_conformer_batch -- utils/diffusion_utils.py:60-78.  pos [n_lig,3] updated in place;
