@@ -217,6 +217,16 @@ int ddmi_sample(ddmi_model* h, float* lig_pos, const ddmi_sample_cfg* cfg, ddmi_
   });
 }
 
+int ddmi_randomize_position(ddmi_model* h, float* lig_pos, const ddmi_randomize_cfg* cfg, ddmi_stream s) {
+  return guard([&] {
+    DDMI_REQUIRE(h && lig_pos && cfg, DDMI_ERR_ARG, "null argument");
+    DDMI_REQUIRE(cfg->struct_size == sizeof(ddmi_randomize_cfg), DDMI_ERR_ARG, "ddmi_randomize_cfg.struct_size does not match this library");
+    DDMI_REQUIRE(cfg->center, DDMI_ERR_ARG, "ddmi_randomize_cfg.center is required");
+    DDMI_CHECK_HIP(hipSetDevice(h->m.device));
+    randomize_position(h->m, lig_pos, *cfg, (hipStream_t)s);
+  });
+}
+
 int ddmi_set_sample_record(ddmi_model* h, const ddmi_sample_record* r) {
   return guard([&] {
     DDMI_REQUIRE(h, DDMI_ERR_ARG, "null model");

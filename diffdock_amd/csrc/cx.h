@@ -100,7 +100,13 @@ struct Model::Cx {
   float *s_tr, *s_rot, *s_tor, *s_t = nullptr; long long* s_ids = nullptr;
   long long* s_ids_host = nullptr; hipEvent_t s_ids_ev = nullptr;   // pinned staging of the sample ids
   bool rec_on = false; ddmi_sample_record rec{};   // ddmi_set_sample_record: caller-owned per-step arrays of the ddmi_sample loop
-  ~Cx() { if (s_ids_host) (void)hipHostFree(s_ids_host); if (s_ids_ev) (void)hipEventDestroy(s_ids_ev); }
+  float *rp_center = nullptr, *rp_center_host = nullptr; hipEvent_t rp_ev = nullptr;   // ddmi_randomize_position: centres [B][3] and their pinned staging
+  ~Cx() {
+    if (s_ids_host) (void)hipHostFree(s_ids_host);
+    if (s_ids_ev) (void)hipEventDestroy(s_ids_ev);
+    if (rp_center_host) (void)hipHostFree(rp_center_host);
+    if (rp_ev) (void)hipEventDestroy(rp_ev);
+  }
 };
 
 typedef Model::Cx Cx;

@@ -382,4 +382,100 @@ void launch_modify_conformer_ragged(float* pos, int B, int maxNl, const int* lig
   DDMI_CHECK_HIP(hipGetLastError());
 }
 
+// ------------------------------------------------------------------ initial poses
+// randomize_position (utils/sampling.py:16-58) for one graph per workgroup (64 threads), in place on the graph's block of pos:
+// sequential torsion rotations WITHOUT re-alignment (modify_conformer_torsion_angles, utils/torsion.py:48-72), then
+// (pos - mean) R^T + centre, then the translation.  Draws the caller does not supply come from philox4x32 at step -1
+// (ddmi_randomize_cfg in include/ddmi.h has the component table).  One kernel serves the batch of copies (a.lig_ptr == nullptr)
+// and the ragged layout, so that a graph's arithmetic is the same instruction stream in both.  smem: 3 * Nl + 32 floats.
+__global__ __launch_bounds__(64) void k_randomize_position(RandomizeArgs a) {
+  DDMI_DYN_SMEM(float, smem);
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int a0 = a.lig_ptr ? a.lig_ptr[b] : b * a.Nl;
+  const int Nl = a.lig_ptr ? a.lig_ptr[b + 1] - a0 : a.Nl;
+  const int t0 = a.lig_ptr ? a.tor_ptr[b] : b * a.R;
+  const int R = a.no_torsion ? 0 : (a.lig_ptr ? a.tor_ptr[b + 1] - t0 : a.R);
+  const int* __restrict__ rot_u = a.rot_u + (a.lig_ptr ? t0 : 0);
+  const int* __restrict__ rot_v = a.rot_v + (a.lig_ptr ? t0 : 0);
+  const unsigned char* __restrict__ mask = R ? a.mask_rotate + (a.lig_ptr ? a.mask_off[b] : 0) : nullptr;
+  const long long sid = a.sample_ids ? a.sample_ids[b] : b;
+  float* __restrict__ p = a.pos + (size_t)a0 * 3;
+  float* x = smem;            // [Nl][3]
+  float* sc = smem + 3 * Nl;  // mean(3), R(9), t(3), -, normals(7), residue index(1)
+  for (int i = tid; i < 3 * Nl; i += 64) x[i] = p[i];
+  if (tid < 7) sc[16 + tid] = normal_draw(a.seed, sid, -1, tid);
+  if (tid == 7) {
+    int idx = 0;
+    if (a.choose_residue) {
+      unsigned o[4];
+      philox4x32((unsigned)sid, (unsigned)((unsigned long long)sid >> 32), (unsigned)-1, 7u, (unsigned)a.seed, (unsigned)(a.seed >> 32), o);
+      const int r0 = a.rec_ptr[b];
+      idx = r0 + (int)(o[0] % (unsigned)(a.rec_ptr[b + 1] - r0));
+    }
+    reinterpret_cast<int*>(sc)[23] = idx;
+  }
+  __syncthreads();
+  for (int j = 0; j < R; ++j) {
+    float th;
+    if (a.tor_updates) th = a.tor_updates[t0 + j];
+    else {   // (2u - 1) pi with u = ((word0 >> 8) + 0.5) / 2^24: every operation below is exact up to the last product, |th| < pi
+      unsigned o[4];
+      philox4x32((unsigned)sid, (unsigned)((unsigned long long)sid >> 32), (unsigned)-1, (unsigned)(8 + j), (unsigned)a.seed,
+                 (unsigned)(a.seed >> 32), o);
+      th = ((float)((int)(o[0] >> 8) - 8388608) + 0.5f) * (3.14159265358979f / 8388608.f);
+    }
+    if (th == 0.f) continue;   // the reference skips an update of exactly 0 (the same decision in every thread)
+    const int u = rot_u[j], v = rot_v[j];
+    const float vx = x[3 * u] - x[3 * v], vy = x[3 * u + 1] - x[3 * v + 1], vz = x[3 * u + 2] - x[3 * v + 2];
+    const float px = x[3 * v], py = x[3 * v + 1], pz = x[3 * v + 2];
+    __syncthreads();
+    const float nrm = sqrtf(vx * vx + vy * vy + vz * vz);
+    float Rm[9];
+    axis_angle_to_matrix(vx / nrm * th, vy / nrm * th, vz / nrm * th, Rm);
+    for (int i = tid; i < Nl; i += 64) {
+      if (!mask[(size_t)j * Nl + i]) continue;
+      const float dx = x[3 * i] - px, dy = x[3 * i + 1] - py, dz = x[3 * i + 2] - pz;
+      x[3 * i] = (Rm[0] * dx + Rm[1] * dy + Rm[2] * dz) + px;
+      x[3 * i + 1] = (Rm[3] * dx + Rm[4] * dy + Rm[5] * dz) + py;
+      x[3 * i + 2] = (Rm[6] * dx + Rm[7] * dy + Rm[8] * dz) + pz;
+    }
+    __syncthreads();
+  }
+  if (tid < 3) {   // molecule centre and translation, one coordinate per thread
+    float s = 0.f;
+    for (int i = 0; i < Nl; ++i) s += x[3 * i + tid];
+    sc[tid] = s / Nl;
+    float t = 0.f;
+    if (!a.no_random) {
+      if (a.tr_updates) t = a.tr_updates[3 * b + tid];
+      else if (a.choose_residue) t = a.rec_pos[3 * (size_t)reinterpret_cast<const int*>(sc)[23] + tid] + 0.01f * sc[20 + tid];
+      else t = a.tr_std * sc[20 + tid];
+    }
+    sc[12 + tid] = t;
+  }
+  if (tid == 3) {
+    if (a.rotations) {
+      for (int i = 0; i < 9; ++i) sc[3 + i] = a.rotations[9 * (size_t)b + i];
+    } else {   // unit quaternion (w, x, y, z) -> matrix
+      const float n = sqrtf(sc[16] * sc[16] + sc[17] * sc[17] + sc[18] * sc[18] + sc[19] * sc[19]);
+      const float w = sc[16] / n, qx = sc[17] / n, qy = sc[18] / n, qz = sc[19] / n;
+      sc[3] = 1 - 2 * (qy * qy + qz * qz); sc[4] = 2 * (qx * qy - qz * w); sc[5] = 2 * (qx * qz + qy * w);
+      sc[6] = 2 * (qx * qy + qz * w); sc[7] = 1 - 2 * (qx * qx + qz * qz); sc[8] = 2 * (qy * qz - qx * w);
+      sc[9] = 2 * (qx * qz - qy * w); sc[10] = 2 * (qy * qz + qx * w); sc[11] = 1 - 2 * (qx * qx + qy * qy);
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < Nl; i += 64) {
+    const float dx = x[3 * i] - sc[0], dy = x[3 * i + 1] - sc[1], dz = x[3 * i + 2] - sc[2];
+    for (int k = 0; k < 3; ++k)
+      p[3 * i + k] = ((sc[3 + 3 * k] * dx + sc[4 + 3 * k] * dy + sc[5 + 3 * k] * dz) + a.center[3 * b + k]) + sc[12 + k];
+  }
+}
+void launch_randomize_position(const RandomizeArgs& a, int maxNl, hipStream_t s) {
+  if (a.B <= 0) return;
+  const size_t smem = (size_t)(3 * maxNl + 32) * sizeof(float);
+  hipLaunchKernelGGL(k_randomize_position, dim3(a.B), dim3(64), smem, s, a);
+  DDMI_CHECK_HIP(hipGetLastError());
+}
+
 }  // namespace ddmi

@@ -366,5 +366,19 @@ void launch_modify_conformer(float* pos, int B, int Nl, int R, const int* rot_u,
 void launch_modify_conformer_ragged(float* pos, int B, int maxNl, const int* lig_ptr, const int* tor_ptr, const int* rot_u,
                                     const int* rot_v, const long long* mask_off, const unsigned char* mask_rotate, const float* tr,
                                     const float* rot, const float* tor, float* rec_pos, hipStream_t s);
+// randomize_position (utils/sampling.py:16-58), one workgroup per graph, pos in place.  lig_ptr == nullptr: a batch of copies (Nl atoms
+// and R rotatable bonds per graph, one mask, tor_updates [B][R]); else the ragged layout addressed as k_modify_conformer_ragged
+// (rot_u / rot_v graph-local, mask block at mask_off[b], tor_updates [n_tor]).  tor_updates / rotations / tr_updates: nullptr = drawn
+// from the generator at step -1.  rec_ptr / rec_pos are read with choose_residue only.
+struct RandomizeArgs {
+  float* pos; int B, Nl, R;
+  const int *lig_ptr, *tor_ptr, *rot_u, *rot_v; const long long* mask_off; const unsigned char* mask_rotate;
+  const int* rec_ptr; const float* rec_pos;
+  const float* center;   // device [B][3]
+  int no_torsion, no_random, choose_residue; float tr_std;
+  unsigned long long seed; const long long* sample_ids;
+  const float *tor_updates, *rotations, *tr_updates;
+};
+void launch_randomize_position(const RandomizeArgs& a, int maxNl, hipStream_t s);
 
 }  // namespace ddmi

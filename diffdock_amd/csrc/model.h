@@ -177,5 +177,7 @@ void set_sample_record(Model& m, const ddmi_sample_record* r);   // nullptr = of
 void sample(Model& m, float* lig_pos, const ddmi_sample_cfg& sc, hipStream_t s);
 // NaN guard + score / noise combination of step k (utils/sampling.py:117-186) on score arrays, in place
 void perturb(Model& m, float* tr, float* rot, float* tor, const ddmi_sample_cfg& sc, int k, hipStream_t s);
+// initial poses (utils/sampling.py:16-58) of every graph of the batch, in place
+void randomize_position(Model& m, float* lig_pos, const ddmi_randomize_cfg& rc, hipStream_t s);
 
 }  // namespace ddmi

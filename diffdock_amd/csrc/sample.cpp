@@ -123,6 +123,39 @@ void perturb(Model& m, float* tr, float* rot, float* tor, const ddmi_sample_cfg&
   perturb_step(m, tr, rot, tor, sc, k, upload_sample_ids(m, sc.sample_ids, s), s);
 }
 
+void randomize_position(Model& m, float* lig_pos, const ddmi_randomize_cfg& rc, hipStream_t s) {
+  DDMI_REQUIRE(m.has_complex, DDMI_ERR_STATE, "ddmi_set_complex must precede ddmi_randomize_position");
+  Cx& c = *m.cx;
+  DDMI_REQUIRE(c.layout || (c.uniform && c.Nl_one > 0), DDMI_ERR_STATE,
+               "randomize_position needs a batch of copies of one complex, or ddmi_set_batch_layout for a batch of several");
+  const bool torsion = !rc.no_torsion && c.nT > 0;
+  DDMI_REQUIRE(!torsion || (c.layout ? c.mask_all != nullptr : c.mask_rotate != nullptr), DDMI_ERR_STATE,
+               "the batch has rotatable bonds and mask_rotate was not provided to ddmi_set_complex");
+  // the centres ride through a pinned staging buffer as the sample ids do: consumed before this returns, nothing waits for the stream
+  if (!c.rp_center) {
+    c.rp_center = m.cpool.alloc<float>((size_t)3 * c.B);
+    DDMI_CHECK_HIP(hipHostMalloc(reinterpret_cast<void**>(&c.rp_center_host), (size_t)3 * c.B * sizeof(float)));
+    DDMI_CHECK_HIP(hipEventCreate(&c.rp_ev));
+  } else {
+    DDMI_CHECK_HIP(hipEventSynchronize(c.rp_ev));
+  }
+  for (int i = 0; i < 3 * c.B; ++i) c.rp_center_host[i] = rc.center[i];
+  DDMI_CHECK_HIP(hipMemcpyAsync(c.rp_center, c.rp_center_host, (size_t)3 * c.B * sizeof(float), hipMemcpyHostToDevice, s));
+  DDMI_CHECK_HIP(hipEventRecord(c.rp_ev, s));
+  RandomizeArgs a{};
+  a.pos = lig_pos; a.B = c.B;
+  if (c.layout) {
+    a.lig_ptr = c.lig_ptr; a.tor_ptr = c.tor_ptr; a.rot_u = c.rot_lu; a.rot_v = c.rot_lv; a.mask_off = c.mask_off; a.mask_rotate = c.mask_all;
+  } else {
+    a.Nl = c.Nl_one; a.R = c.R_one; a.rot_u = c.rot_u; a.rot_v = c.rot_v; a.mask_rotate = c.mask_rotate;
+  }
+  a.rec_ptr = c.rec_ptr; a.rec_pos = c.rec_pos; a.center = c.rp_center;
+  a.no_torsion = !torsion; a.no_random = rc.no_random != 0; a.choose_residue = rc.choose_residue != 0; a.tr_std = rc.tr_std;
+  a.seed = rc.seed; a.sample_ids = upload_sample_ids(m, rc.sample_ids, s);
+  a.tor_updates = rc.tor_updates; a.rotations = rc.rotations; a.tr_updates = rc.tr_updates;
+  launch_randomize_position(a, c.layout ? c.maxNl : c.Nl_one, s);
+}
+
 void sample(Model& m, float* lig_pos, const ddmi_sample_cfg& sc, hipStream_t s) {
   DDMI_REQUIRE(m.has_complex, DDMI_ERR_STATE, "ddmi_set_complex must precede ddmi_sample");
   check_sample_cfg(m, sc);

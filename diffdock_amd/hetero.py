@@ -164,6 +164,49 @@ class HeteroBatch(HeteroData):
         out._globals["_slices"] = {nt: offsets[nt] + [out[nt].num_nodes] for nt in node_types}
         return out
 
+    @classmethod
+    def replicate(cls, graph: HeteroData, n: int, device=None) -> "HeteroBatch":
+        """The collated batch of n copies of one graph, element for element what
+        `from_data_list([graph.clone() for _ in range(n)]).to(device)` gives, built without the n host clones: every tensor is
+        moved to `device` once and repeated there, edge indices get an arange offset per copy (graph-major order, as collation
+        concatenates them).  Non-tensor attributes (mask_rotate, name) become lists of n references to the graph's own object:
+        the form a batch of copies has (MIScoreModel._ensure_complex recognises it), and nothing the path mutates in place."""
+        if n < 1:
+            raise ValueError("replicate: n must be positive")
+        out = cls()
+
+        def mv(v):
+            return v if device is None else v.to(device)
+
+        def rep(v):
+            return mv(v).repeat(n, *([1] * (v.dim() - 1)))
+        num = {nt: graph[nt].num_nodes for nt in graph.node_types}
+        for nt in graph.node_types:
+            st = out[nt]
+            for k in list(graph[nt].keys()):
+                v = graph[nt][k]
+                st[k] = rep(v) if torch.is_tensor(v) else [v] * n
+            st["batch"] = mv(torch.arange(n, dtype=torch.long)).repeat_interleave(num[nt])
+            st["ptr"] = mv(torch.arange(n + 1, dtype=torch.long)) * num[nt]
+        for et in graph.edge_types:
+            st = out[et]
+            for k in list(graph[et].keys()):
+                v = graph[et][k]
+                if k == "edge_index":
+                    ei = mv(v)
+                    step = torch.tensor([[num[et[0]]], [num[et[2]]]], dtype=v.dtype, device=ei.device)
+                    copy_of = torch.arange(n, dtype=v.dtype, device=ei.device).repeat_interleave(v.shape[1])
+                    st[k] = ei.repeat(1, n) + step * copy_of
+                elif torch.is_tensor(v):
+                    st[k] = rep(v)
+                else:
+                    st[k] = [v] * n
+        for k, v in graph._globals.items():
+            out._globals[k] = rep(v) if torch.is_tensor(v) and v.dim() > 0 else [v] * n
+        out._globals["num_graphs"] = n
+        out._globals["_slices"] = {nt: [i * num[nt] for i in range(n + 1)] for nt in graph.node_types}
+        return out
+
     def to_data_list(self) -> List[HeteroData]:
         B = self.num_graphs
         sl = self._globals["_slices"]

@@ -139,6 +139,12 @@ class SampleRecord(C.Structure):   # ddmi_sample_record (include/ddmi.h)
                 ("rot", C.c_void_p), ("tor", C.c_void_p), ("nan_count", C.c_void_p)]
 
 
+class RandomizeCfg(C.Structure):   # ddmi_randomize_cfg (include/ddmi.h)
+    _fields_ = [("struct_size", C.c_uint32), ("no_torsion", C.c_int32), ("no_random", C.c_int32), ("choose_residue", C.c_int32),
+                ("tr_std", C.c_float), ("center", C.c_void_p), ("seed", C.c_uint64), ("sample_ids", C.c_void_p),
+                ("tor_updates", C.c_void_p), ("rotations", C.c_void_p), ("tr_updates", C.c_void_p)]
+
+
 def make_config(cfg) -> Config:
     c = Config()
     for name, _ in Config._fields_:
@@ -183,6 +189,7 @@ _DECLS = {
     "ddmi_modify_conformer": (C.c_int, [C.c_void_p] + [C.c_void_p] * 4 + [C.c_void_p]),
     "ddmi_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(SampleCfg), C.c_void_p]),
     "ddmi_set_sample_record": (C.c_int, [C.c_void_p, C.POINTER(SampleRecord)]),
+    "ddmi_randomize_position": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RandomizeCfg), C.c_void_p]),
     "ddmi_perturb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SampleCfg), C.c_int, C.c_void_p]),
     "ddmi_debug_shape": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ddmi_debug_read": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -316,6 +316,74 @@ class MIScoreModel:
                                                             self._stream()))
         return out
 
+    def randomize_position(self, data, no_torsion, no_random, tr_sigma_max, initial_noise_std_proportion=-1.0,
+                           choose_residue=False, center=None, seed=0, sample_ids=None, draws=None):
+        """randomize_position (utils/sampling.py:16-58, the argument order of the reference) for every graph of the collated
+        batch, on the device (ddmi_randomize_position): returns the initial poses [n_lig, 3]; `data` is left as it is.
+
+        center: None = the mean residue position of graph 0, used for every graph as the reference uses data_list[0]'s (the batch
+        must then hold copies of one complex); or [3] / [B, 3], e.g. the pocket centre of `pocket_knowledge`, which the caller
+        computes with the reference's rule (utils/sampling.py:20-29).  The translation std is computed here from the reference's two
+        formulas (std_rec * prop / 1.73 with std_rec of graph 0's receptor, or -prop * tr_sigma_max).  Draws: keyed by
+        (seed, sample id, step -1, component) as include/ddmi.h lists them, `sample_ids` = one id per graph (default 0..B-1), so a
+        pose does not depend on how the run is batched or sharded; or injected through `draws` = dict(torsion=[per graph: R
+        angles], rotation=[per graph: 3x3], tr=[per graph: (1,3) translation]) as synth.randomize_position takes them (any
+        subset)."""
+        self._ensure_complex(data)
+        dev = self.device
+        B = self._B
+        n0 = int(self._keep["rec_ptr"][1])
+        rec0 = None   # graph 0's residues on the host (float32 torch arithmetic there, as the reference's: the same on every device)
+        if center is None or initial_noise_std_proportion >= 0.0:
+            rec0 = data["receptor"].pos[:n0].detach().to("cpu", torch.float32)
+        if center is None:
+            if not self._copies:
+                raise ValueError("randomize_position: a batch of several complexes needs an explicit center [B, 3]")
+            center = rec0.mean(dim=0)
+        ctr = torch.as_tensor(center).detach().to("cpu", torch.float32).reshape(-1, 3)
+        ctr = np.ascontiguousarray(ctr.expand(B, 3).numpy() if ctr.shape[0] == 1 else ctr.numpy())
+        if ctr.shape != (B, 3):
+            raise ValueError(f"center: [3] or [{B}, 3] expected, got {tuple(ctr.shape)}")
+        rc = _lib.RandomizeCfg()
+        rc.struct_size = C.sizeof(_lib.RandomizeCfg)
+        rc.no_torsion, rc.no_random, rc.choose_residue = int(bool(no_torsion)), int(bool(no_random)), int(bool(choose_residue))
+        if initial_noise_std_proportion >= 0.0:   # utils/sampling.py:52-54
+            if not self._copies and not choose_residue and not no_random:
+                raise ValueError("randomize_position: initial_noise_std_proportion >= 0 scales by one receptor's extent; a batch of "
+                                 "several complexes takes tr_sigma_max (a negative proportion) or injected translations")
+            std_rec = float(torch.sqrt(torch.mean(torch.sum(rec0 ** 2, dim=1))))
+            rc.tr_std = std_rec * initial_noise_std_proportion / 1.73
+        else:
+            rc.tr_std = -initial_noise_std_proportion * tr_sigma_max
+        rc.center = ctr.ctypes.data
+        rc.seed = int(seed)
+        ids = None
+        if sample_ids is not None:
+            ids = np.ascontiguousarray(np.asarray(sample_ids, dtype=np.int64))
+            assert ids.size == B, "one sample id per graph of the batch"
+            rc.sample_ids = ids.ctypes.data
+        injected = []
+        if draws is not None:
+            def dev_f32(parts, shape):
+                t = torch.cat([torch.as_tensor(np.asarray(p, dtype=np.float64)).reshape(-1) for p in parts]) if len(parts) else torch.zeros(0)
+                assert t.numel() == shape, (t.numel(), shape)
+                t = t.to(dev, torch.float32).contiguous()
+                injected.append(t)
+                return t.data_ptr() if t.numel() else None
+            n_tor = 0 if no_torsion else self._n_tor
+            if draws.get("torsion") is not None and n_tor:
+                rc.tor_updates = dev_f32(draws["torsion"], n_tor)
+            if draws.get("rotation") is not None:
+                rc.rotations = dev_f32(draws["rotation"], 9 * B)
+            if draws.get("tr") is not None:
+                rc.tr_updates = dev_f32(draws["tr"], 3 * B)
+        pos = data["ligand"].pos.to(dev, torch.float32).contiguous().clone()
+        _lib.check(self.lib, self.lib.ddmi_randomize_position(self._h, _ptr(pos), C.byref(rc), self._stream()))
+        if dev.type == "cuda":   # the injected draws must outlive the enqueued kernel
+            for t in injected:
+                t.record_stream(torch.cuda.current_stream(dev))
+        return pos
+
     def _sample_cfg(self, inference_steps, schedules, noise, seed, sample_ids, ode, no_random, no_final_step_noise,
                     temp_sampling, temp_psi, temp_sigma_data, crop_beyond):
         """ddmi_sample_cfg + the host / device arrays it points into (returned so that they outlive the call)."""

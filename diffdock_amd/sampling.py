@@ -292,6 +292,98 @@ def sampling(data_list, model, inference_steps, tr_schedule, rot_schedule, tor_s
     return data_list, confidence
 
 
+def sample_poses(complex_graph, n_poses, model, inference_steps, tr_schedule, rot_schedule, tor_schedule, model_args=None,
+                 batch_size=32, seed=0, sample_id_offset=0, initial_noise_std_proportion=-1.0, choose_residue=False, center=None,
+                 confidence_model=None, confidence_graph=None, confidence_model_args=None, no_random=False, ode=False,
+                 no_final_step_noise=False, temp_sampling=1.0, temp_psi=0.0, temp_sigma_data=0.5, return_full_trajectory=False,
+                 visualization_list=None):
+    """inference.py:239-242 + sampling() from ONE complex graph, with nothing per pose on the host: for each chunk of `batch_size`
+    poses the batch is HeteroBatch.replicate(complex_graph, b) on the model's device, the initial poses are drawn there
+    (model.randomize_position: no_torsion of the score model, no_random=False as inference.py passes them, sample ids
+    sample_id_offset + lo + i), and model.sample_batch runs the step loop with the same ids, seed and crop_beyond handling as
+    sampling().  Returns (pos, confidence) -- pos float32 [n_poses, n, 3] on the device, centred as the model sees it; confidence
+    as sampling() returns it (None without a confidence model) -- and with `return_full_trajectory=True` a third value, the
+    trajectory [inference_steps + 1, n_poses, n, 3] as sampling() defines it.  `no_random` ... `temp_sigma_data` are sampling()'s.
+
+    With the initial poses of model.randomize_position written into n_poses clones, sampling(..., seed=seed,
+    batch_size=batch_size) gives these poses bit for bit.
+
+    center: None = mean residue position of the complex (the reference's default); or the pocket centre of `pocket_knowledge`.
+    Confidence: the confidence model scores replicate(confidence_graph or complex_graph, b) with the final poses, at t = 0 with a
+    confidence graph and at the last step's times without one (sampling()'s rule).  confidence_model_args.crop_beyond runs as the
+    device crop (confidence_model.set_crop_cutoff) around each pose instead of sampling()'s per-graph host crop: the same kept
+    residues, and a pose that keeps no residue is scored from its ligand rows alone instead of getting NaN.
+
+    `visualization_list` is not served here (sampling() feeds it), nor are several complexes at once (sample_complexes)."""
+    if visualization_list is not None:
+        raise NotImplementedError("sample_poses does not feed a visualization_list: sampling() does (utils/sampling.py:193-206)")
+    if n_poses < 1 or batch_size < 1:
+        raise ValueError("n_poses and batch_size must be positive")
+    if not hasattr(model, "randomize_position") or not hasattr(model, "sample_batch"):
+        raise NotImplementedError("sample_poses needs a model with randomize_position and sample_batch (MIScoreModel)")
+    cfg = model.cfg if model_args is None else model_args
+    crop = getattr(model_args, "crop_beyond", None) if model_args is not None else getattr(model.cfg, "crop_beyond", None)
+    conf_crop = getattr(confidence_model_args, "crop_beyond", None) if confidence_model_args is not None else None
+    schedules = (np.asarray(tr_schedule, dtype=np.float64), np.asarray(rot_schedule, dtype=np.float64),
+                 np.asarray(tor_schedule, dtype=np.float64))
+    device = getattr(model, "device", None)
+    n = int(complex_graph["ligand"].pos.shape[0])
+    name = _complex_name(complex_graph)
+    if center is None:
+        center = complex_graph["receptor"].pos.mean(dim=0)
+    batches, conf_batches = {}, {}   # one replicated batch per chunk size: the model keeps its static part between chunks
+
+    def batch_of(cache, graph, b):
+        if b not in cache:
+            cache.clear()
+            cache[b] = HeteroBatch.replicate(graph, b, device)
+            cache[b]["ligand"].pos0 = cache[b]["ligand"].pos   # the conformer every chunk starts from
+        return cache[b]
+    poses, confidence, trajectory = [], [] if confidence_model is not None else None, []
+    with torch.no_grad():
+        for lo in range(0, n_poses, batch_size):
+            b = min(batch_size, n_poses - lo)
+            ids = list(range(sample_id_offset + lo, sample_id_offset + lo + b))
+            batch = batch_of(batches, complex_graph, b)
+            batch["ligand"].pos = batch["ligand"].pos0   # a batch kept from the chunk before carries that chunk's poses
+            pos0 = model.randomize_position(batch, cfg.no_torsion, False, cfg.tr_sigma_max,
+                                            initial_noise_std_proportion=initial_noise_std_proportion,
+                                            choose_residue=choose_residue, center=center, seed=seed, sample_ids=ids)
+            batch["ligand"].pos = pos0
+            pos, step_pos, nan_count = _sample_batch(
+                model, return_full_trajectory, batch, inference_steps, schedules, seed=seed, sample_ids=ids, ode=ode,
+                no_random=no_random, no_final_step_noise=no_final_step_noise, temp_sampling=temp_sampling, temp_psi=temp_psi,
+                temp_sigma_data=temp_sigma_data, crop_beyond=crop)
+            _warn_nans(nan_count, [name], [lo // batch_size + 1], [b])
+            if return_full_trajectory:
+                trajectory.append(torch.cat([pos0[None], step_pos], 0).reshape(inference_steps + 1, b, n, 3))
+            poses.append(pos.reshape(b, n, 3))
+            if confidence_model is None:
+                continue
+            if confidence_graph is not None:
+                cbatch = batch_of(conf_batches, confidence_graph, b)
+                t = (0, 0, 0)
+            else:   # the sampling graph, still carrying the last step's times (utils/sampling.py:113-114, 223)
+                cbatch = batch
+                t = (schedules[0][-1], schedules[1][-1], schedules[2][-1])
+            cbatch["ligand"].pos = pos
+            set_time(cbatch, *t, b, device=pos.device)
+            if conf_crop is not None and confidence_graph is not None:   # sampling() crops confidence graphs only (utils/sampling.py:213-217)
+                confidence_model.set_crop_cutoff(conf_crop)
+            try:
+                out = confidence_model(cbatch)
+            finally:
+                if conf_crop is not None and confidence_graph is not None:
+                    confidence_model.set_crop_cutoff(None)
+            confidence.append(out[0] if isinstance(out, tuple) else out)
+    pos = torch.cat(poses, 0)
+    if confidence is not None:
+        confidence = torch.nan_to_num(torch.cat(confidence, dim=0), nan=-1000)
+    if return_full_trajectory:
+        return pos, confidence, torch.cat(trajectory, 1)
+    return pos, confidence
+
+
 def _pack(chunks, max_batch_graphs):
     """Whole chunks, in order, into device batches of at most max_batch_graphs graphs (a larger chunk runs alone)."""
     batches, cur, n = [], [], 0

@@ -323,6 +323,36 @@ int ddmi_set_sample_record(ddmi_model* m, const ddmi_sample_record* r); /* NULL 
 int ddmi_perturb(ddmi_model* m, float* tr, float* rot, float* tor, const ddmi_sample_cfg* cfg, int step,
                  ddmi_stream stream);
 
+/* randomize_position -- utils/sampling.py:16-58 (inference.py:239-242) for every graph of the batch, on the device.  lig_pos
+ * [n_lig,3] is updated in place, one workgroup per graph: the rotatable bonds in edge order, each rotating the atoms of its
+ * mask_rotate row about pos[v] by the axis-angle (pos[u] - pos[v]) / |..| * angle (modify_conformer_torsion_angles,
+ * utils/torsion.py:48-72: an angle of exactly 0 is skipped, no re-alignment); then (pos - mean) R^T + center; then, unless
+ * no_random, the translation.  Works on a batch of copies of one complex and under ddmi_set_batch_layout; a graph's result
+ * depends on nothing but its own inputs and its sample id.  No host synchronisation; the host arrays are consumed before the
+ * call returns.
+ * Draws the caller does not supply come from the library's Philox4x32-10 block with counter (sample id low word, sample id
+ * high word, step, component) and key = seed, at step = -1 (0xffffffff as the unsigned counter word: no loop step has it):
+ *   component 0-3    standard normals (w, x, y, z), as ddmi_debug_normal gives them; the normalised quaternion is the rotation
+ *                    R = [[1-2(yy+zz), 2(xy-zw), 2(xz+yw)], [2(xy+zw), 1-2(xx+zz), 2(yz-xw)], [2(xz-yw), 2(yz+xw), 1-2(xx+yy)]]
+ *   component 4-6    standard normals z of the translation: tr_std * z, or with choose_residue rec_pos[idx] + 0.01 * z
+ *   component 7      output word 0 modulo the graph's residue count = idx, the choose_residue residue (within the graph)
+ *   component 8 + j  rotatable bond j of the graph: u = ((word 0 >> 8) + 0.5) / 2^24, angle = (2u - 1) pi
+ * Sharded runs and the tests rely on this layout.
+ * DDMI_ERR_STATE: no complex set; a batch whose graphs differ without a layout; rotatable bonds without mask_rotate.
+ * DDMI_ERR_ARG: struct_size mismatch, NULL center. */
+typedef struct ddmi_randomize_cfg {
+  uint32_t struct_size;       /* sizeof(ddmi_randomize_cfg) the caller was built against                                  */
+  int32_t no_torsion, no_random, choose_residue;
+  float tr_std;               /* host-computed: std_rec * prop / 1.73, or -prop * tr_sigma_max (utils/sampling.py:52-57) */
+  const float* center;        /* HOST [B,3]: center_pocket of each graph                                                  */
+  uint64_t seed;
+  const int64_t* sample_ids;  /* HOST [B] or NULL (= 0..B-1)                                                              */
+  const float* tor_updates;   /* device [n_tor] angles, graphs in order, or NULL                                          */
+  const float* rotations;     /* device [B,3,3] row-major or NULL                                                         */
+  const float* tr_updates;    /* device [B,3] or NULL: the complete translation, replaces draw and mode                   */
+} ddmi_randomize_cfg;
+int ddmi_randomize_position(ddmi_model* m, float* lig_pos, const ddmi_randomize_cfg* cfg, ddmi_stream stream);
+
 /* Introspection for tests and profiling: copy a named internal buffer to the host.
  * ddmi_debug_shape returns the element count and up to 4 dims; names are listed in DESIGN.md. */
 int ddmi_debug_shape(ddmi_model* m, const char* name, int64_t shape[4], int* ndim, int* is_int);
