@@ -301,6 +301,33 @@ int ddmi_debug_normal(uint64_t seed, int64_t sample0, int n_samples, int step, i
   });
 }
 
+int ddmi_debug_reduce_bn_sum(int n_groups, int n_nodes, int d_in, int d_out, const int32_t* toff, const float* msg, const float* bn_mean,
+                             const float* bn_scale, const float* bn_bias, const float* x_in, float* x_out, float* ref_out, ddmi_stream s) {
+  return guard([&] {
+    DDMI_REQUIRE(n_groups >= 1 && n_groups <= REDUCE_SUM_MAX && n_nodes > 0 && d_in >= 0 && d_in <= d_out && d_out <= XS, DDMI_ERR_ARG,
+                 "bad sizes");
+    DDMI_REQUIRE(toff && msg && bn_mean && bn_scale && bn_bias && x_in && x_out, DDMI_ERR_ARG, "null argument");
+    DDMI_REQUIRE(!ref_out || n_groups == 1, DDMI_ERR_ARG, "ref_out: one group only");
+    ReduceSumArgs a{};
+    a.n_groups = n_groups;
+    for (int g = 0; g < n_groups; ++g)
+      a.g[g] = ReduceSumGroup{toff + (size_t)g * (n_nodes + 1), msg, bn_mean + (size_t)g * d_out, bn_scale + (size_t)g * d_out,
+                              bn_bias + (size_t)g * d_out};
+    a.nbase = 0; a.ncount = n_nodes; a.D_in = d_in; a.D_out = d_out; a.X_in = x_in; a.X_out = x_out;
+    launch_reduce_bn_sum(a, (hipStream_t)s);
+    if (!ref_out) return;
+    struct Buf {   // freed on every exit path
+      ReduceGroup* p = nullptr;
+      Buf() { DDMI_CHECK_HIP(hipMalloc(reinterpret_cast<void**>(&p), sizeof(ReduceGroup))); }
+      ~Buf() { if (p) (void)hipFree(p); }
+    } rg;
+    const ReduceGroup g0{toff, msg, 0, n_nodes};
+    DDMI_CHECK_HIP(hipMemcpyAsync(rg.p, &g0, sizeof(g0), hipMemcpyHostToDevice, (hipStream_t)s));
+    launch_reduce_bn(rg.p, 1, 0, n_nodes, d_in, d_out, bn_mean, bn_scale, bn_bias, 1, x_in, ref_out, XS, (hipStream_t)s);
+    DDMI_CHECK_HIP(hipStreamSynchronize((hipStream_t)s));
+  });
+}
+
 int ddmi_set_kernel_timing(ddmi_model* h, int enabled) {
   if (!h) return DDMI_ERR_ARG;
   resolve_timings(h->m);

@@ -143,10 +143,12 @@ static void receptor_constants(Model& m, const ddmi_complex& cc, const std::vect
     float* emb = dalloc<float>(m, nullptr, {c.nA, ns});
     launch_lig_node_embed(c.atom_x, c.nA, m.atom_emb, m.atom_emb_off, 4, ns, emb, s);
     launch_add_rowvec(c.atom_node_base, XS, emb, ns, nullptr, 0, nullptr, c.nA, ns, 0, s);
-    launch_edge_mlp(mlp_args(m.atom_edge, ns, c.Eaa, nullptr, c.aa_dist, m.off_lig, m.D, m.coeff_lig, 0, m.atom_edge.b0, nullptr,
-                             c.atom_edge_base), s);
-    launch_edge_mlp(mlp_args(m.ar_edge, ns, c.Ear, nullptr, c.ar_dist, m.off_rec, m.D, m.coeff_rec, 0, m.ar_edge.b0, nullptr,
-                             c.ar_edge_base), s);
+    if (!cfg.old_model) {   // (the legacy class feeds sigma into these MLPs: per forward, forward_old_aa)
+      launch_edge_mlp(mlp_args(m.atom_edge, ns, c.Eaa, nullptr, c.aa_dist, m.off_lig, m.D, m.coeff_lig, 0, m.atom_edge.b0, nullptr,
+                               c.atom_edge_base), s);
+      launch_edge_mlp(mlp_args(m.ar_edge, ns, c.Ear, nullptr, c.ar_dist, m.off_rec, m.D, m.coeff_rec, 0, m.ar_edge.b0, nullptr,
+                               c.ar_edge_base), s);
+    }
   }
   c.rec_node_enc = nullptr;
   if (!m.rec_emb_layers.empty() && cfg.all_atoms) {
@@ -440,6 +442,10 @@ void set_complex(Model& m, const ddmi_complex& cc, hipStream_t s) {
   c.ll_gvec = dalloc<float>(m, nullptr, {B, ns}); c.cross_gvec = dalloc<float>(m, nullptr, {B, ns});
   c.center_gvec = dalloc<float>(m, nullptr, {B, ns}); c.tr_sig = dalloc<float>(m, nullptr, {B, ns});
   c.rr_sig_old = dalloc<float>(m, nullptr, {B, ns});
+  if (cfg.old_model && cfg.all_atoms) {
+    c.atom_sig = dalloc<float>(m, nullptr, {B, ns}); c.aa_sig_old = dalloc<float>(m, nullptr, {B, ns});
+    c.ar_sig_old = dalloc<float>(m, nullptr, {B, ns});
+  }
   if (cfg.atom_confidence && cfg.confidence_mode) {
     c.ac_in = dalloc<float>(m, nullptr, {nL, 2 * ns}); c.ac_h0 = dalloc<float>(m, nullptr, {nL, ns});
     c.ac_h1 = dalloc<float>(m, nullptr, {nL, ns}); c.ac_out = dalloc<float>(m, nullptr, {nL, cfg.atom_num_confidence_outputs + ns});
@@ -482,7 +488,7 @@ void set_complex(Model& m, const ddmi_complex& cc, hipStream_t s) {
   }
   for (size_t l = 0; l < m.conv_layers.size(); ++l) c.rb_l.push_back(dalloc<float>(m, nullptr, {B, H}));
   std::vector<const ConvW*> all_layers;
-  for (auto* fam : {&m.conv_layers, &m.lig_emb_layers, &m.rec_emb_layers, &m.old_lig, &m.old_rec, &m.old_l2r, &m.old_r2l})
+  for (auto* fam : {&m.conv_layers, &m.lig_emb_layers, &m.rec_emb_layers, &m.old_lig, &m.old_rec, &m.old_l2r, &m.old_r2l, &m.old_aa})
     for (auto& L : *fam) all_layers.push_back(&L);
   {
     int HKq = 0;

@@ -517,7 +517,7 @@ void run_conv(Model& m, const ConvW& L, const std::vector<RunGroup>& groups, con
   const LayerPlan P = plan_layer(m, L, groups.data(), n, pq_mode, false);
   if (P.runner == LayerPlan::grouped) {
     run_groups_grouped(m, L, groups.data(), P, Xin, s);
-    node_update(m, L, rg_dev, n_rg, nbase, ncount, Xin, Xout, s, Lnext, gnext);
+    if (rg_dev) node_update(m, L, rg_dev, n_rg, nbase, ncount, Xin, Xout, s, Lnext, gnext);
     return;
   }
   if (P.mm_all && pq_mode != 2) launch_fc1_terms(m, L, groups.data(), P, 0, n, Xin, s);
@@ -537,7 +537,7 @@ void run_conv(Model& m, const ConvW& L, const std::vector<RunGroup>& groups, con
     DDMI_CHECK_HIP(hipEventRecord(m.ev_join, m.side_stream));
     DDMI_CHECK_HIP(hipStreamWaitEvent(s, m.ev_join, 0));
   }
-  node_update(m, L, rg_dev, n_rg, nbase, ncount, Xin, Xout, s, Lnext, gnext);
+  if (rg_dev) node_update(m, L, rg_dev, n_rg, nbase, ncount, Xin, Xout, s, Lnext, gnext);
 }
 
 // The interaction layers of the CG model over [ll ; lig<-rec ; rec-rec ; rec<-lig] (cg_model.py:329-349), from table c.X[xi] on.

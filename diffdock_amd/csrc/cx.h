@@ -38,6 +38,7 @@ struct Model::Cx {
   float *temb, *hidB, *rec_sig, *ligsig, *ll_gvec, *cross_gvec, *center_gvec, *tr_sig, *rot_sig, *cutoff, *rr_rowbias;
   float *ac_in = nullptr, *ac_h0 = nullptr, *ac_h1 = nullptr, *ac_out = nullptr;   // atom_confidence_predictor activations [nL, .]
   float* rr_sig_old = nullptr;   // legacy classes: sigma term of the receptor edge embedding (old_cg_model.py:411-413)
+  float *atom_sig = nullptr, *aa_sig_old = nullptr, *ar_sig_old = nullptr;   // legacy all-atom class: sigma terms of the atom rows and of the two static atom relations' edge embeddings
   float* embsum;
   std::vector<float*> X;
   int *adjrank, *cnt_g, *cnt_t, *goff_ll, *toff_ll, *ll_tgt, *ll_tslot, *ll_featidx, *ll_batch;
@@ -167,7 +168,8 @@ struct RunGroup {
 // pq_mode: 0 = the per-node terms of the first Linear as the size rule says (per group, or batched for small layers), 1 = all of
 // them in one launch in front of the groups (first layer of the fused node-update route), 2 = already there (written by the
 // previous layer's k_node_update).  Lnext / gnext: the NEXT interaction layer and its groups -- the node update then also
-// produces their per-node terms (k_node_update instead of k_reduce_bn).
+// produces their per-node terms (k_node_update instead of k_reduce_bn).  rg_dev == nullptr: the groups' messages only, the caller
+// reduces them (legacy all-atom class: several modules meet in one node update, k_reduce_bn_sum).
 void run_conv(Model& m, const ConvW& L, const std::vector<RunGroup>& groups, const ReduceGroup* rg_dev, int n_rg,
               const float* Xin, float* Xout, int nbase, int ncount, hipStream_t s, int pq_mode = 0, const ConvW* Lnext = nullptr,
               const std::vector<RunGroup>* gnext = nullptr);

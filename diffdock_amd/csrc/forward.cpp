@@ -301,6 +301,181 @@ static void run_aa_layers(Model& m, const float* lig_pos, const RunGroup& g_ll, 
   }
 }
 
+// legacy confidence head (old_cg_model.py:283-291 = old_aa_model.py:284-295) on the final ligand rows
+static void old_confidence_head(Model& m, const float* XL, int D_last, int n_out, float* conf_out, hipStream_t s) {
+  Cx& c = *m.cx;
+  const int Lc = m.cfg.num_conv_layers;
+  ConfHeadArgs a{};
+  a.B = c.B; a.X = XL; a.ldx = XS; a.col0 = 0; a.lig_ptr = c.lig_ptr; a.ns = m.ns;
+  a.n_tail = Lc >= 3 ? m.ns : 0;
+  a.tail_off = D_last - a.n_tail;
+  a.W0 = m.conf_W[0]; a.b0 = m.conf_b[0]; a.sc0 = m.conf_bn_scale[0]; a.sh0 = m.conf_bn_shift[0];
+  a.W1 = m.conf_W[1]; a.b1 = m.conf_b[1]; a.sc1 = m.conf_bn_scale[1]; a.sh1 = m.conf_bn_shift[1];
+  a.W2 = m.conf_W[2]; a.b2 = m.conf_b[2]; a.n_out = n_out; a.out = conf_out;
+  launch_conf_head(a, s);
+}
+
+// ============================================================ legacy all-atom class
+// models/old_aa_model.py:202-348 (AAOldModel.forward, score and confidence mode): ligand, residue and atom rows from OldAtomEncoders,
+// six edge embeddings that all carry the sigma embedding of edge_index[0]'s graph, and per interaction layer nine separate
+// OldTensorProductConvLayers conv_layers[9l + k] -- each its own fc, tensor product, mean over its own edges and BatchNorm -- three of
+// which meet in every node type: X_{l+1}[type] = pad(X_l[type]) + u1 + u2 + u3 (k_reduce_bn_sum).  The last layer runs the three
+// ligand modules only.  crop: as run_aa_layers -- the residues beyond the cutoff and their atoms lose every edge (masks in the pair
+// searches, the static relations through their compaction); their rows stay in the tables and nothing reads them.
+static void forward_old_aa(Model& m, const float* lig_pos, const float* t_tr, const float* t_rot, const float* t_tor, float* tr_out,
+                           float* rot_out, float* tor_out, float* conf_out, hipStream_t s) {
+  Cx& c = *m.cx;
+  const ddmi_config& cfg = m.cfg;
+  const int ns = m.ns, sd = m.sd, B = c.B, nL = c.nL, nR = c.nR, nA = c.nA, aB = nL + nR, Lc = cfg.num_conv_layers;
+  const bool conf = cfg.confidence_mode != 0, crop = m.crop_cutoff > 0.0;
+  DDMI_REQUIRE(!crop || c.ar_arange, DDMI_ERR_ARG,
+               "crop_beyond of an all-atom complex needs one atom_rec_edge_index column per atom, column k for atom k (n_atom_rec_edges == "
+               "n_atom, row 0 == 0..n_atom-1): the reference rewrites the relation as arange(kept atoms) (utils/utils.py:395-399)");
+  ++c.epoch;
+  PhaseTimer t_fwd(m, "forward_total", s);
+  std::unique_ptr<PhaseTimer> t_phase(new PhaseTimer(m, "embed_and_graphs", s));
+  launch_time_embedding(t_tr, B, m.time_freq, sd / 2, cfg.embedding_scale, cfg.embedding_type, c.temb, s);
+  {   // everything linear in the sigma embedding, one launch: OldAtomEncoder.linear of the three node types (the receptor's through
+      // the sigma columns of lm_embedding_layer, as forward_old), the sigma columns of the six edge embeddings, the read-outs' terms
+    struct Term { const float* W; int ldw; const float* bias; float* C; };
+    const bool lm = m.lm > 0;
+    const Term terms[] = {{m.old_lig_lin.W0, sd, m.old_lig_lin.b0, c.ligsig},
+                          {lm ? m.old_lm_W + ns + m.lm - sd : m.old_rec_lin.W0, lm ? ns + m.lm : sd, lm ? nullptr : m.old_rec_lin.b0, c.rec_sig},
+                          {m.old_atom_lin.W0, sd, m.old_atom_lin.b0, c.atom_sig},
+                          {m.lig_edge.W0 + m.nf, m.lig_edge.in, m.lig_edge.b0, c.ll_gvec},
+                          {m.rec_edge.W0, m.rec_edge.in, m.rec_edge.b0, c.rr_sig_old},
+                          {m.atom_edge.W0, m.atom_edge.in, m.atom_edge.b0, c.aa_sig_old},
+                          {m.cross_edge.W0, m.cross_edge.in, m.cross_edge.b0, c.cross_gvec},
+                          {m.ar_edge.W0, m.ar_edge.in, m.ar_edge.b0, c.ar_sig_old},
+                          {m.la_edge.W0, m.la_edge.in, m.la_edge.b0, c.la_gvec},
+                          // score mode only (old_aa_model.py:299-300,311-322)
+                          {m.center_edge.W0 + m.D, m.center_edge.in, m.center_edge.b0, c.center_gvec},
+                          {m.tr_final.W0 + 1, 1 + sd, m.tr_final.b0, c.tr_sig},
+                          {m.rot_final.W0 + 1, 1 + sd, m.rot_final.b0, c.rot_sig}};
+    GemmBatch gb;
+    for (const Term& q : terms) {
+      if (gb.n == (conf ? 9 : 12)) break;
+      GemmArgs& x = gb.g[gb.n++];
+      x.A = c.temb; x.lda = sd; x.W = q.W; x.ldw = q.ldw; x.bias = q.bias; x.C = q.C; x.ldc = ns; x.M = B; x.N = ns; x.K = sd;
+    }
+    launch_gemm_batch(gb, s);
+  }
+  // ---- node table [lig | rec | atom]: static embedding sums + the per-graph sigma term
+  float* X0 = c.X[0];
+  launch_lig_node_embed(c.lig_x, nL, m.lig_emb, m.lig_emb_off, 16, ns, c.embsum, s);
+  launch_add_rowvec(X0, XS, c.embsum, ns, c.ligsig, ns, c.lig_batch, nL, ns, ns, s);
+  launch_add_rowvec(X0 + (size_t)nL * XS, XS, c.rec_node_base, XS, c.rec_sig, ns, c.rec_batch, nR, ns, ns, s);
+  launch_add_rowvec(X0 + (size_t)aB * XS, XS, c.atom_node_base, XS, c.atom_sig, ns, c.atom_batch, nA, ns, ns, s);
+  // ---- per-step crop: residue and atom masks, the four static relations re-compacted under them (as forward)
+  if (crop) {
+    const double cd = m.crop_cutoff;
+    {
+      PhaseTimer t(m, "k_crop_mask", s);
+      launch_crop_mask(lig_pos, c.rec_pos, c.rec_batch, c.lig_ptr, nR, (float)(cd * cd), c.keep, s);
+      launch_crop_atom_mask(c.keep, c.atom_res, nA, c.keep_atom, s);
+    }
+    RelFilterArgs fa;
+    fa.r[fa.n++] = RelFilter{c.keep, c.keep, nR, nR, nL, c.rr_goff, c.rr_tgt, c.rr_arow, c.rr_toff, c.rr_tlist, c.rr_gnode,
+                             c.cnt_g2, c.cnt_t2, c.goff2, c.toff2, c.tslot_tmp, c.tgt2, c.tslot2, c.arow2};
+    auto add = [&](const Cx::StaticEdges& e, const int* gkeep, int gn, const int* tkeep, int tn, int tbase) {
+      fa.r[fa.n++] = RelFilter{gkeep, tkeep, gn, tn, tbase, e.goff, e.tgt, e.arow, e.toff, e.tlist, e.gnode,
+                               e.cnt_g, e.cnt_t, e.goff2, e.toff2, e.tslot_tmp, e.tgt2, e.tslot2, e.arow2};
+    };
+    add(c.se_aa, c.keep_atom, nA, c.keep_atom, nA, aB);
+    add(c.se_ar, c.keep, nR, c.keep_atom, nA, aB);
+    add(c.se_ra, c.keep_atom, nA, c.keep, nR, nL);
+    PhaseTimer t(m, "k_rel_filter", s);
+    launch_rel_filter(fa, s);
+  }
+  // ---- graphs and edge embeddings.  Distance expansions (old_aa_model.py:440,462,476,485): atom-atom through the LIGAND one,
+  // lig-atom through the CROSS one, atom-rec through the receptor one
+  lig_graph(m, lig_pos, s);
+  launch_edge_mlp(mlp_args(m.rec_edge, ns, c.Err, nullptr, c.rr_dist, m.off_rec, m.D, m.coeff_rec, sd, c.rr_sig_old, c.rr_batch,
+                           c.rec_edge_base), s);
+  launch_edge_mlp(mlp_args(m.atom_edge, ns, c.Eaa, nullptr, c.aa_dist, m.off_lig, m.D, m.coeff_lig, sd, c.aa_sig_old, c.aa_batch,
+                           c.atom_edge_base), s);
+  launch_edge_mlp(mlp_args(m.ar_edge, ns, c.Ear, nullptr, c.ar_dist, m.off_rec, m.D, m.coeff_rec, sd, c.ar_sig_old, c.ar_batch,
+                           c.ar_edge_base), s);
+  const float* cut_dev = nullptr;
+  if (cfg.dynamic_max_cross) {   // confidence mode feeds the raw t as sigma (old_aa_model.py:206-209,227)
+    launch_cross_cutoff(t_tr, B, cfg.tr_sigma_min, cfg.tr_sigma_max, c.cutoff, s, conf ? 1 : 0);
+    cut_dev = c.cutoff;
+  }
+  launch_cross_count(lig_pos, c.rec_pos, c.lig_batch, c.rec_batch, c.lig_ptr, c.rec_ptr, nL, nR, c.maxNr, cut_dev,
+                     cfg.cross_max_distance, crop ? c.keep : nullptr, c.pairrank, c.cnt_l, c.cnt_r, s);
+  launch_exclusive_scan2(c.cnt_l, c.offs_l, nL, c.cnt_r, c.offs_r, nR, s);
+  launch_cross_fill(lig_pos, c.rec_pos, c.rec_batch, c.lig_ptr, c.rec_ptr, nL, nR, c.maxNr, c.pairrank, c.offs_l, c.offs_r,
+                    cut_dev, cfg.cross_max_distance, cfg.smooth_edges, c.g1_tgt, c.g1_tslot, c.g3_tgt, c.g3_tslot, c.pbatch,
+                    c.pdist, c.pnvec, c.pew, s);
+  launch_edge_mlp(mlp_args(m.cross_edge, ns, c.Elr_cap, c.offs_l + nL, c.pdist, m.off_cross, m.Dc, m.coeff_cross, sd,
+                           c.cross_gvec, c.pbatch, c.cross_ea), s);
+  launch_cross_count(lig_pos, c.atom_pos, c.lig_batch, c.atom_batch, c.lig_ptr, c.atom_ptr, nL, nA, c.maxNa, nullptr,
+                     cfg.lig_max_radius, crop ? c.keep_atom : nullptr, c.la_pairrank, c.la_cnt_l, c.la_cnt_a, s);
+  launch_exclusive_scan2(c.la_cnt_l, c.la_offs_l, nL, c.la_cnt_a, c.la_offs_a, nA, s);
+  launch_cross_fill(lig_pos, c.atom_pos, c.atom_batch, c.lig_ptr, c.atom_ptr, nL, nA, c.maxNa, c.la_pairrank, c.la_offs_l,
+                    c.la_offs_a, nullptr, cfg.lig_max_radius, cfg.smooth_edges, c.la1_tgt, c.la1_tslot, c.la3_tgt, c.la3_tslot,
+                    c.la_pbatch, c.la_dist, c.la_nvec, c.la_ew, s, aB);
+  launch_edge_mlp(mlp_args(m.la_edge, ns, c.Ela_cap, c.la_offs_l + nL, c.la_dist, m.off_cross, m.Dc, m.coeff_cross, sd, c.la_gvec,
+                           c.la_pbatch, c.la_ea), s);
+  // ---- the nine modules of a layer in the reference's order (old_aa_model.py:236-271); every first Linear sees
+  // [edge, target, gathered], the flipped ones reuse the forward spherical harmonics
+  const Rel rr = crop ? Rel{c.goff2, c.tgt2, c.tslot2, c.arow2} : Rel{c.rr_goff, c.rr_tgt, c.rr_tslot, c.rr_arow};
+  const Rel ra = rel_of(c.se_ra, crop), aa = rel_of(c.se_aa, crop), ar = rel_of(c.se_ar, crop);
+  RunGroup g[9] = {
+      {0, nL, 0, nL, c.goff_ll, c.ll_tgt, c.ll_tslot, nullptr, c.ll_ea, c.Ell_cap, c.goff_ll + nL, nullptr, nullptr, c.ll_nvec,
+       c.ll_ew, 1.f, c.msg_aa[0]},                                                                                  // 9l + 0  lig <- lig
+      {nL, nR, 0, nL, c.offs_r, c.g1_tgt, c.g1_tslot, c.g1_tslot, c.cross_ea, c.Elr_cap, c.offs_l + nL, nullptr, nullptr, c.pnvec,
+       c.pew, 1.f, c.msg_aa[1]},                                                                                    // 9l + 1  lig <- rec
+      {aB, nA, 0, nL, c.la_offs_a, c.la1_tgt, c.la1_tslot, c.la1_tslot, c.la_ea, c.Ela_cap, c.la_offs_l + nL, nullptr, nullptr,
+       c.la_nvec, c.la_ew, 1.f, c.msg_aa[2]},                                                                       // 9l + 2  lig <- atom
+      {aB, nA, aB, nA, aa.goff, aa.tgt, aa.tslot, aa.arow, c.atom_edge_base, c.Eaa, nullptr, nullptr, nullptr, c.aa_nvec, c.aa_ew,
+       1.f, c.msg_aa[6]},                                                                                           // 9l + 3  atom <- atom
+      {0, nL, aB, nA, c.la_offs_l, c.la3_tgt, c.la3_tslot, nullptr, c.la_ea, c.Ela_cap, c.la_offs_l + nL, nullptr, nullptr,
+       c.la_nvec, c.la_ew, 1.f, c.msg_aa[7]},                                                                       // 9l + 4  atom <- lig
+      {nL, nR, aB, nA, ar.goff, ar.tgt, ar.tslot, ar.arow, c.ar_edge_base, c.Ear, nullptr, nullptr, nullptr, c.ar_nvec, nullptr,
+       1.f, c.msg_aa[8]},                                                                                           // 9l + 5  atom <- rec
+      {nL, nR, nL, nR, rr.goff, rr.tgt, rr.tslot, rr.arow, c.rec_edge_base, c.Err, nullptr, nullptr, nullptr, c.rr_nvec, c.rr_ew,
+       1.f, c.msg_aa[3]},                                                                                           // 9l + 6  rec <- rec
+      {0, nL, nL, nR, c.offs_l, c.g3_tgt, c.g3_tslot, nullptr, c.cross_ea, c.Elr_cap, c.offs_l + nL, nullptr, nullptr, c.pnvec,
+       c.pew, 1.f, c.msg_aa[4]},                                                                                    // 9l + 7  rec <- lig
+      {aB, nA, nL, nR, ra.goff, ra.tgt, ra.tslot, ra.arow, c.ar_edge_base, c.Ear, nullptr, nullptr, nullptr, c.ar_nvec, nullptr,
+       1.f, c.msg_aa[5]}};                                                                                          // 9l + 8  rec <- atom
+  static const int vn_of[9] = {2, 0, 4, 6, 7, 8, 1, 3, 5};   // virtual-node list of every module (set_complex)
+  for (int k = 0; k < 9; ++k) g[k].vn = vn_of[k];
+  g[0].load = g[4].load = g[7].load = true;
+  g[3].static_topo = g[5].static_topo = g[6].static_topo = g[8].static_topo = !crop;
+  // target-order offsets of the nine modules' messages
+  const int* toff[9] = {c.toff_ll, c.offs_l, c.la_offs_l,
+                        crop ? c.se_aa.toff2 : c.se_aa.toff, c.la_offs_a, crop ? c.se_ar.toff2 : c.se_ar.toff,
+                        crop ? c.toff2 : c.rr_toff, c.offs_r, crop ? c.se_ra.toff2 : c.se_ra.toff};
+  t_phase.reset();
+  for (int l = 0; l < Lc; ++l) {
+    const bool last = l == Lc - 1;
+    const float* Xin = c.X[l];
+    const int n_mod = last ? 3 : 9;
+    for (int k = 0; k < n_mod; ++k) run_conv(m, m.old_aa[9 * l + k], {g[k]}, nullptr, 0, Xin, nullptr, 0, 0, s);
+    PhaseTimer t(m, "k_reduce_bn_sum", s);
+    // summed in the reference's order: lig + lig_update + la + lr ; atom + atom_update + al + ar ; rec + rec_update + ra + rl
+    static const int order[3][3] = {{0, 2, 1}, {3, 4, 5}, {6, 8, 7}};
+    const int base[3] = {0, aB, nL}, count[3] = {nL, nA, nR};
+    for (int ty = 0; ty < (last ? 1 : 3); ++ty) {
+      ReduceSumArgs a{};
+      a.n_groups = 3;
+      for (int j = 0; j < 3; ++j) {
+        const int k = order[ty][j];
+        const BnArgs bn = bn_args(m.old_aa[9 * l + k]);
+        a.g[j] = ReduceSumGroup{toff[k], g[k].msg, bn.mean, bn.scale, bn.bias};
+      }
+      a.nbase = base[ty]; a.ncount = count[ty]; a.D_in = m.old_aa[9 * l].D_in; a.D_out = m.old_aa[9 * l].D_out;
+      a.X_in = Xin; a.X_out = c.X[l + 1];
+      launch_reduce_bn_sum(a, s);
+    }
+  }
+  PhaseTimer t_read(m, "readouts", s);
+  if (conf) old_confidence_head(m, c.X[Lc], m.old_aa[9 * (Lc - 1)].D_out, cfg.num_confidence_outputs + (cfg.affinity_prediction ? 1 : 0), conf_out, s);
+  else score_readouts(m, c.X[Lc], lig_pos, t_tr, t_rot, t_tor, tr_out, rot_out, tor_out, s);
+}
+
 // cg_model.py:353-366: graph-mean of the even (and, from 3 layers on, the odd) scalars -> confidence_predictor
 static void confidence_readout(Model& m, const float* XL, float* conf_out, float* atom_conf_out, hipStream_t s) {
   Cx& c = *m.cx;
@@ -337,7 +512,10 @@ void forward(Model& m, const float* lig_pos, const float* t_tr, const float* t_r
   DDMI_REQUIRE(conf == (conf_out != nullptr), DDMI_ERR_STATE, "score models use ddmi_forward, confidence models ddmi_confidence");
   DDMI_REQUIRE(conf || !m.cfg.scale_by_sigma || (m.so3_table && (m.cfg.no_torsion || m.torus_table)), DDMI_ERR_STATE,
                "score-norm tables not set (ddmi_set_table)");
-  if (m.cfg.old_model) { forward_old(m, lig_pos, t_tr, t_rot, t_tor, tr_out, rot_out, tor_out, conf_out, s); return; }
+  if (m.cfg.old_model) {
+    (m.cfg.all_atoms ? forward_old_aa : forward_old)(m, lig_pos, t_tr, t_rot, t_tor, tr_out, rot_out, tor_out, conf_out, s);
+    return;
+  }
   Cx& c = *m.cx;
   const ddmi_config& cfg = m.cfg;
   const int ns = m.ns, sd = m.sd, B = c.B, nL = c.nL, nR = c.nR;

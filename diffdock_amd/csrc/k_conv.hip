@@ -423,4 +423,72 @@ void launch_reduce_bn(const ReduceGroup* groups_dev, int n_groups, int nbase, in
   DDMI_CHECK_HIP(hipGetLastError());
 }
 
+// ---------------------------------------------------------------------- reduce + BN, summed over separate modules
+// Node update of the legacy all-atom class (models/old_aa_model.py:273-281): up to three OldTensorProductConvLayers write into one
+// node type, each with its own mean over its own edges and its own BatchNorm, summed onto the zero-padded input row:
+//   X_out[s] = pad(X_in[s]) + sum_g BN_g(mean of group g's messages into s);  no incoming edge: BN_g(0) (scatter-mean of nothing = 0).
+// One workgroup per target node as k_reduce_bn: wave w sums rows b + w, b + w + 4, ... of a group in that kernel's order, a lane 4
+// consecutive columns per 16-B streaming load; every group has its own four partial rows in LDS, so one barrier serves all of
+// them.  Every message row is read once, every output row written once (k_reduce_bn per module + k_add3: three table round trips).
+__global__ __launch_bounds__(256) void k_reduce_bn_sum(const ReduceSumArgs a) {
+  __shared__ float red[REDUCE_SUM_MAX][4][XS + 4];
+  const int sl = blockIdx.x, s = a.nbase + sl;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = DDMI_UNIFORM(tid >> 6);
+  const bool live = 4 * lane < a.D_out;
+  int cnt[REDUCE_SUM_MAX];
+#pragma unroll
+  for (int g = 0; g < REDUCE_SUM_MAX; ++g) {
+    cnt[g] = 0;
+    if (g >= a.n_groups) continue;
+    const int b = a.g[g].toff[sl], e = a.g[g].toff[sl + 1];
+    cnt[g] = e - b;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (live) {
+      const float* __restrict__ mp = a.g[g].msg + 4 * lane;
+      int r = b + wave;
+      for (; r + 12 < e; r += 16) {
+        const float4 v0 = nt_load4(mp + (size_t)r * XS), v1 = nt_load4(mp + (size_t)(r + 4) * XS);
+        const float4 v2 = nt_load4(mp + (size_t)(r + 8) * XS), v3 = nt_load4(mp + (size_t)(r + 12) * XS);
+        acc.x += v0.x; acc.y += v0.y; acc.z += v0.z; acc.w += v0.w;   // k_reduce_bn's order
+        acc.x += v1.x; acc.y += v1.y; acc.z += v1.z; acc.w += v1.w;
+        acc.x += v2.x; acc.y += v2.y; acc.z += v2.z; acc.w += v2.w;
+        acc.x += v3.x; acc.y += v3.y; acc.z += v3.z; acc.w += v3.w;
+      }
+      for (; r < e; r += 4) {
+        const float4 v0 = nt_load4(mp + (size_t)r * XS);
+        acc.x += v0.x; acc.y += v0.y; acc.z += v0.z; acc.w += v0.w;
+      }
+    }
+    if (4 * lane < XS) *reinterpret_cast<float4*>(&red[g][wave][4 * lane]) = acc;
+  }
+  __syncthreads();
+  const int c = tid;
+  if (c >= XS) return;
+  float out = 0.f;
+  if (c < a.D_out) {
+#pragma unroll
+    for (int g = 0; g < REDUCE_SUM_MAX; ++g) {
+      if (g >= a.n_groups) continue;
+      const float sum = (red[g][0][c] + red[g][1][c]) + (red[g][2][c] + red[g][3][c]);
+      float v = cnt[g] > 0 ? sum / (float)cnt[g] : 0.f;
+      if (a.g[g].bn_scale) v = (v - a.g[g].bn_mean[c]) * a.g[g].bn_scale[c] + a.g[g].bn_bias[c];
+      if (g == 0) {
+        if (c < a.D_in) v += a.X_in[(size_t)s * XS + c];
+        out = v;
+      } else {
+        out += v;
+      }
+    }
+  }
+  a.X_out[(size_t)s * XS + c] = out;
+}
+
+void launch_reduce_bn_sum(const ReduceSumArgs& a, hipStream_t s) {
+  if (a.ncount <= 0) return;
+  if (a.n_groups < 1 || a.n_groups > REDUCE_SUM_MAX) throw Error(DDMI_ERR_ARG, "k_reduce_bn_sum: one to three groups");
+  hipLaunchKernelGGL(k_reduce_bn_sum, dim3(a.ncount), dim3(256), 0, s, a);
+  DDMI_CHECK_HIP(hipGetLastError());
+}
+
 }  // namespace ddmi

@@ -185,6 +185,18 @@ void launch_reduce_bn(const ReduceGroup* groups_dev, int n_groups, int nbase, in
                       const float* bn_mean, const float* bn_scale, const float* bn_bias, int residual,
                       const float* X_in, float* X_out, int out_stride, hipStream_t s);
 
+// Node update over SEPARATE modules (legacy all-atom class): X_out[s] = pad(X_in[s]) + sum_g BN_g(mean of group g's messages into s)
+// for the nodes s = nbase + i, i in [0, ncount); group g's rows of node i are [toff[i], toff[i + 1]) of msg.  bn_mean / bn_scale /
+// bn_bias: D_out-wide folded BatchNorm of the group's module (all null: none).  One group = launch_reduce_bn with residual, bit for bit.
+constexpr int REDUCE_SUM_MAX = 3;
+struct ReduceSumGroup { const int* toff; const float* msg; const float *bn_mean, *bn_scale, *bn_bias; };
+struct ReduceSumArgs {
+  int n_groups; ReduceSumGroup g[REDUCE_SUM_MAX];
+  int nbase, ncount, D_in, D_out;
+  const float* X_in; float* X_out;   // node tables, row stride XS
+};
+void launch_reduce_bn_sum(const ReduceSumArgs& a, hipStream_t s);
+
 // Fused node update (k_node.hip): launch_reduce_bn for the rows [nbase, nbase + ncount) of a layer AND, from the finished rows,
 // the per-node terms of the NEXT layer's first Linear: term t writes out_t[s - base_t][H] = W_t[H][ldw-strided rows] . X_out[s][:ns]
 // (+ bias_t) for the nodes s in [base_t, base_t + count_t) -- the P / Q rows k_edge_hidden_mm adds per edge.

@@ -120,7 +120,8 @@ struct Model {
   std::vector<ConvW> rec_emb_layers, lig_emb_layers, conv_layers;
   ConvW final_conv, tor_conv;
   std::vector<ConvW> old_lig, old_rec, old_l2r, old_r2l;   // legacy class: four separate layers per interaction layer
-  Mlp2W old_lig_lin, old_rec_lin;                          // OldAtomEncoder.linear (W0/b0 only)
+  std::vector<ConvW> old_aa;                               // legacy all-atom class: nine modules per layer, conv_layers.{9l + k}
+  Mlp2W old_lig_lin, old_rec_lin, old_atom_lin;            // OldAtomEncoder.linear (W0/b0 only)
   float *old_lm_W = nullptr, *old_lm_b = nullptr;          // OldAtomEncoder.lm_embedding_layer [ns][1280 + ns]
   float *tor_W0 = nullptr, *tor_W3 = nullptr;
   float* side_Mt = nullptr; int side_K = 0;   // sidechain_predictor as one dense [10][side_K] matrix over a node row (weights.cpp)

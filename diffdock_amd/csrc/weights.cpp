@@ -185,8 +185,7 @@ void build_weight_spec(Model& m) {
     }
   };
   if (c.old_model) {   // models/old_cg_model.py:18-200, models/layers.py:70-118, models/tensor_layers.py:338-380
-    DDMI_REQUIRE(c.sh_lmax == 2 && !c.all_atoms && K == 0, DDMI_ERR_ARG,
-                 "legacy class: sh_lmax = 2, CG graphs, no embedding layers");
+    DDMI_REQUIRE(c.sh_lmax == 2 && K == 0, DDMI_ERR_ARG, "legacy classes: sh_lmax = 2, no embedding layers");
     DDMI_REQUIRE(c.embedding_type == 0, DDMI_ERR_ARG, "legacy class: sinusoidal timestep embedding only");
     auto old_encoder = [&](const std::string& n, const int* dims, int nd, bool lm) {
       for (int i = 0; i < nd; ++i) S.push_back({n + ".atom_embedding_list." + std::to_string(i) + ".weight", {dims[i], ns}});
@@ -197,7 +196,15 @@ void build_weight_spec(Model& m) {
     mlp("lig_edge_embedding", m.nf + sd + m.D, ns, ns);
     old_encoder("rec_node_embedding", REC_DIMS, 1, m.lm > 0);
     mlp("rec_edge_embedding", sd + m.D, ns, ns);
-    mlp("cross_edge_embedding", sd + m.Dc, ns, ns);
+    if (c.all_atoms) {   // models/old_aa_model.py:73-78
+      old_encoder("atom_node_embedding", ATOM_DIMS, 4, false);
+      mlp("atom_edge_embedding", sd + m.D, ns, ns);
+      mlp("lr_edge_embedding", sd + m.Dc, ns, ns);
+      mlp("ar_edge_embedding", sd + m.D, ns, ns);
+      mlp("la_edge_embedding", sd + m.Dc, ns, ns);
+    } else {
+      mlp("cross_edge_embedding", sd + m.Dc, ns, ns);
+    }
     S.push_back({"lig_distance_expansion.offset", {m.D}});
     S.push_back({"rec_distance_expansion.offset", {m.D}});
     S.push_back({"cross_distance_expansion.offset", {m.Dc}});
@@ -207,12 +214,20 @@ void build_weight_spec(Model& m) {
     std::vector<ConvW>* fams[4] = {&m.old_lig, &m.old_rec, &m.old_l2r, &m.old_r2l};
     const char* names[4] = {"lig_conv_layers.", "rec_conv_layers.", "lig_to_rec_conv_layers.", "rec_to_lig_conv_layers."};
     for (int f = 0; f < 4; ++f) {
-      fams[f]->assign(Lc, ConvW());
-      for (int l = 0; l < Lc; ++l) {
+      fams[f]->assign(c.all_atoms ? 0 : Lc, ConvW());
+      for (int l = 0; l < (int)fams[f]->size(); ++l) {
         init_conv_meta(c, (*fams[f])[l], names[f] + std::to_string(l), layer_irreps(co, l), sh, layer_irreps(co, l + 1), 3 * ns, 1,
                        false, false, true);
         conv((*fams[f])[l]);
       }
+    }
+    // AAOldModel (models/old_aa_model.py:100-117): nine modules per layer, conv_layers.{9l + k}; the module owns k = 3..8 of the
+    // last layer too, which its forward never runs (:248,277) -- they are keys all the same
+    m.old_aa.assign(c.all_atoms ? 9 * Lc : 0, ConvW());
+    for (int i = 0; i < (int)m.old_aa.size(); ++i) {
+      init_conv_meta(c, m.old_aa[i], "conv_layers." + std::to_string(i), layer_irreps(co, i / 9), sh, layer_irreps(co, i / 9 + 1), 3 * ns,
+                     1, false, false, true);
+      conv(m.old_aa[i]);
     }
     if (!c.confidence_mode) {   // score mode of the legacy class: the read-outs of old_cg_model.py:156-200
       readout_spec(layer_irreps(co, Lc));
@@ -220,7 +235,9 @@ void build_weight_spec(Model& m) {
     }
     lin("confidence_predictor.0", Lc >= 3 ? 2 * ns : ns, ns);
     lin("confidence_predictor.4", ns, ns);
-    lin("confidence_predictor.8", ns, c.affinity_prediction ? 2 : 1);
+    if (c.all_atoms) DDMI_REQUIRE(c.num_confidence_outputs >= 1, DDMI_ERR_ARG, "num_confidence_outputs must be >= 1");
+    // (CGOldModel is built with one confidence output; AAOldModel with num_confidence_outputs, old_aa_model.py:120-127)
+    lin("confidence_predictor.8", ns, (c.all_atoms ? c.num_confidence_outputs : 1) + (c.affinity_prediction ? 1 : 0));
     for (int i : {1, 5})
       for (const char* k : {".weight", ".bias", ".running_mean", ".running_var"})
         S.push_back({"confidence_predictor." + std::to_string(i) + k, {ns}});
@@ -654,6 +671,21 @@ static void commit_readouts(Model& m) {
   }
 }
 
+// receptor-atom encoder: the four embedding tables concatenated (both all-atom classes)
+static void upload_atom_tables(Model& m) {
+  std::vector<float> emb;
+  std::vector<int> off;
+  int rows = 0;
+  for (int i = 0; i < 4; ++i) {
+    off.push_back(rows);
+    const HostTensor& t = W(m, "atom_node_embedding.atom_embedding_list." + std::to_string(i) + ".weight");
+    emb.insert(emb.end(), t.data.begin(), t.data.end());
+    rows += ATOM_DIMS[i];
+  }
+  m.atom_emb = m.wpool.upload(emb);
+  m.atom_emb_off = m.wpool.upload(off);
+}
+
 void commit_weights(Model& m) {
   for (auto& kv : m.spec) {
     auto it = m.host_w.find(kv.first);
@@ -687,7 +719,14 @@ void commit_weights(Model& m) {
     if (m.lm > 0) { m.old_lm_W = up(m, "rec_node_embedding.lm_embedding_layer.weight"); m.old_lm_b = up(m, "rec_node_embedding.lm_embedding_layer.bias"); }
     m.lig_edge = up_mlp(m, "lig_edge_embedding");
     m.rec_edge = up_mlp(m, "rec_edge_embedding");
-    m.cross_edge = up_mlp(m, "cross_edge_embedding");
+    m.cross_edge = up_mlp(m, c.all_atoms ? "lr_edge_embedding" : "cross_edge_embedding");
+    if (c.all_atoms) {
+      upload_atom_tables(m);
+      m.old_atom_lin.W0 = up(m, "atom_node_embedding.linear.weight"); m.old_atom_lin.b0 = up(m, "atom_node_embedding.linear.bias");
+      m.atom_edge = up_mlp(m, "atom_edge_embedding");
+      m.ar_edge = up_mlp(m, "ar_edge_embedding");
+      m.la_edge = up_mlp(m, "la_edge_embedding");
+    }
     if (c.confidence_mode) {
       for (int i = 0; i < 3; ++i) {
         m.conf_W[i] = up(m, "confidence_predictor." + std::to_string(4 * i) + ".weight");
@@ -713,6 +752,8 @@ void commit_weights(Model& m) {
     offs_old("cross_distance_expansion.offset", m.off_cross, m.coeff_cross);
     for (auto* fam : {&m.old_lig, &m.old_rec, &m.old_l2r, &m.old_r2l})
       for (auto& L : *fam) commit_conv(m, L);
+    for (int i = 0; i < (int)m.old_aa.size(); ++i)   // (the six modules of the last layer no forward runs stay on the host)
+      if (i / 9 < c.num_conv_layers - 1 || i % 9 < 3) commit_conv(m, m.old_aa[i]);
     if (!c.confidence_mode) {
       offs_old("center_distance_expansion.offset", m.off_center, m.coeff_center);
       commit_readouts(m);
@@ -736,17 +777,7 @@ void commit_weights(Model& m) {
   m.rec_sigma = up_mlp(m, "rec_sigma_embedding");
   m.cross_edge = up_mlp(m, c.all_atoms ? "lr_edge_embedding" : "cross_edge_embedding");
   if (c.all_atoms) {
-    std::vector<float> emb;
-    std::vector<int> off;
-    int rows = 0;
-    for (int i = 0; i < 4; ++i) {
-      off.push_back(rows);
-      const HostTensor& t = W(m, "atom_node_embedding.atom_embedding_list." + std::to_string(i) + ".weight");
-      emb.insert(emb.end(), t.data.begin(), t.data.end());
-      rows += ATOM_DIMS[i];
-    }
-    m.atom_emb = m.wpool.upload(emb);
-    m.atom_emb_off = m.wpool.upload(off);
+    upload_atom_tables(m);
     m.atom_edge = up_mlp(m, "atom_edge_embedding");
     m.ar_edge = up_mlp(m, "ar_edge_embedding");
     m.la_edge = up_mlp(m, "la_edge_embedding");

@@ -510,17 +510,21 @@ def get_model(args, device, t_to_sigma=None, no_parallel=True, confidence_mode=F
     compatibility; the geometric schedule it implements (utils/diffusion_utils.py:28-32) is evaluated
     in-library from the sigma bounds in `args`."""
     cfg = args if isinstance(args, ModelConfig) else config_from_args(args)
-    if old:   # utils/utils.py:180-219: CGOldModel; no sh_lmax / embedding-layer / pseudoscalar arguments reach it
-        if cfg.all_atoms:
-            raise NotImplementedError("the legacy classes are built on CG graphs only (models/old_cg_model.py)")
+    if old:   # utils/utils.py:180-219: CGOldModel, or AAOldModel on all-atom graphs; no sh_lmax / embedding-layer / pseudoscalar
+        # arguments reach either; rec_max_radius and center_max_distance keep the class defaults (30 / 30 = ModelConfig's)
+        parallel = getattr(args, "parallel", 1) if not isinstance(args, ModelConfig) else 1
+        if parallel not in (1, None):   # (config_from_args refuses it for a namespace; kept here for any other args object)
+            raise NotImplementedError("get_model arguments outside the built path: parallel > 1")
         cfg = cfg.replace(old=True, confidence_mode=bool(confidence_mode), sh_lmax=2, num_prot_emb_layers=0,
                           depthwise_convolution=False, sidechain_pred=False,   # (not among the arguments get_model(old=True) passes, utils/utils.py:180-219)
-                          reduce_pseudoscalars=False, num_confidence_outputs=1,
+                          reduce_pseudoscalars=False,
+                          # CGOldModel has one confidence output; AAOldModel as many as get_model passes (old_aa_model.py:120-127)
+                          num_confidence_outputs=cfg.num_confidence_outputs if cfg.all_atoms else 1,
                           use_old_atom_encoder=getattr(args, "use_old_atom_encoder", True) if not isinstance(args, ModelConfig)
                           else cfg.use_old_atom_encoder)
         if not cfg.use_old_atom_encoder:
-            raise NotImplementedError("CGOldModel with the new AtomEncoder cannot be constructed by the reference either "
-                                      "(AtomEncoder has no lm_embedding_type argument)")
+            raise NotImplementedError(("AAOldModel" if cfg.all_atoms else "CGOldModel") + " with the new AtomEncoder cannot be "
+                                      "constructed by the reference either (AtomEncoder has no lm_embedding_type argument)")
     elif not cfg.embed_also_ligand and not cfg.all_atoms:
         # CGModel.ligand_embedding asserts it on every forward (models/cg_model.py:263, "otherwise reimplement padding").
         # AAModel has no such assert: without ligand embedding layers it zero-pads the ligand rows to the receptor width

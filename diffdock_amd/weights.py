@@ -151,9 +151,10 @@ def _readout_spec(cfg, spec, lin, mlp, conv, last_out, sh):
 
 
 def _old_spec(cfg, spec, lin, mlp, bn, conv):
-    """models/old_cg_model.py:18-200 (CGOldModel + OldAtomEncoder + OldTensorProductConvLayer), score or confidence mode."""
-    assert cfg.use_old_atom_encoder and cfg.sh_lmax == 2 and not cfg.all_atoms, \
-        "legacy class: OldAtomEncoder, sh_lmax = 2 (get_model(old=True) passes no sh_lmax), CG graphs"
+    """models/old_cg_model.py:18-200 (CGOldModel + OldAtomEncoder + OldTensorProductConvLayer) and, with all_atoms,
+    models/old_aa_model.py:21-200 (AAOldModel), score or confidence mode."""
+    assert cfg.use_old_atom_encoder and cfg.sh_lmax == 2, \
+        "legacy classes: OldAtomEncoder, sh_lmax = 2 (get_model(old=True) passes no sh_lmax)"
     ns, sd = cfg.ns, cfg.sigma_embed_dim
 
     def old_encoder(name, dims, lm):
@@ -166,26 +167,41 @@ def _old_spec(cfg, spec, lin, mlp, bn, conv):
     mlp("lig_edge_embedding", cfg.in_lig_edge_features + sd + cfg.distance_embed_dim, ns, ns)
     old_encoder("rec_node_embedding", REC_RESIDUE_FEATURE_DIMS, cfg.lm_embedding_type is not None)
     mlp("rec_edge_embedding", sd + cfg.distance_embed_dim, ns, ns)
-    mlp("cross_edge_embedding", sd + cfg.cross_distance_embed_dim, ns, ns)
+    if cfg.all_atoms:   # old_aa_model.py:73-78
+        old_encoder("atom_node_embedding", REC_ATOM_FEATURE_DIMS, False)
+        mlp("atom_edge_embedding", sd + cfg.distance_embed_dim, ns, ns)
+        mlp("lr_edge_embedding", sd + cfg.cross_distance_embed_dim, ns, ns)
+        mlp("ar_edge_embedding", sd + cfg.distance_embed_dim, ns, ns)
+        mlp("la_edge_embedding", sd + cfg.cross_distance_embed_dim, ns, ns)
+    else:
+        mlp("cross_edge_embedding", sd + cfg.cross_distance_embed_dim, ns, ns)
     spec["lig_distance_expansion.offset"] = ((cfg.distance_embed_dim,), "offset:lig")
     spec["rec_distance_expansion.offset"] = ((cfg.distance_embed_dim,), "offset:rec")
     spec["cross_distance_expansion.offset"] = ((cfg.cross_distance_embed_dim,), "offset:cross")
     sh = sh_irreps(2)
     old_cfg = cfg.replace(reduce_pseudoscalars=False)
-    for fam in ("lig_conv_layers", "rec_conv_layers", "lig_to_rec_conv_layers", "rec_to_lig_conv_layers"):
-        for l in range(cfg.num_conv_layers):
-            a, b = old_cfg.layer_irreps(l)
-            W = tp_weight_numel(a, sh, b, False)
-            lin(f"{fam}.{l}.fc.0", 3 * ns, 3 * ns)
-            lin(f"{fam}.{l}.fc.3", 3 * ns, W)
-            if cfg.batch_norm:
-                bn(f"{fam}.{l}.batch_norm", b)
+
+    def old_conv(name, l):
+        a, b = old_cfg.layer_irreps(l)
+        W = tp_weight_numel(a, sh, b, False)
+        lin(f"{name}.fc.0", 3 * ns, 3 * ns)
+        lin(f"{name}.fc.3", 3 * ns, W)
+        if cfg.batch_norm:
+            bn(f"{name}.batch_norm", b)
+    if cfg.all_atoms:   # nine modules per layer (old_aa_model.py:100-117); the last layer's 3..8 exist and never run (:248,277)
+        for i in range(9 * cfg.num_conv_layers):
+            old_conv(f"conv_layers.{i}", i // 9)
+    else:
+        for fam in ("lig_conv_layers", "rec_conv_layers", "lig_to_rec_conv_layers", "rec_to_lig_conv_layers"):
+            for l in range(cfg.num_conv_layers):
+                old_conv(f"{fam}.{l}", l)
     if not cfg.confidence_mode:
         _readout_spec(old_cfg, spec, lin, mlp, conv, old_cfg.layer_irreps(cfg.num_conv_layers - 1)[1], sh)
         return spec
     lin("confidence_predictor.0", 2 * ns if cfg.num_conv_layers >= 3 else ns, ns)
     lin("confidence_predictor.4", ns, ns)
-    lin("confidence_predictor.8", ns, 2 if cfg.affinity_prediction else 1)
+    # (CGOldModel is built with one confidence output, AAOldModel with num_confidence_outputs: old_aa_model.py:120-127)
+    lin("confidence_predictor.8", ns, (cfg.num_confidence_outputs if cfg.all_atoms else 1) + (1 if cfg.affinity_prediction else 0))
     for i in (1, 5):
         spec[f"confidence_predictor.{i}.weight"] = ((ns,), "bn_w")
         spec[f"confidence_predictor.{i}.bias"] = ((ns,), "bn_b")

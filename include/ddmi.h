@@ -126,7 +126,10 @@ typedef struct ddmi_config {
   int32_t confidence_mode, num_confidence_outputs;
   /* get_model(..., old=True) (utils/utils.py:180-219): legacy class models/old_cg_model.py (the released DiffDock-L
    * confidence checkpoint, `old_confidence_model: true`).  Score mode (ddmi_forward, old_cg_model.py:293-352) and confidence
-   * mode (ddmi_confidence), OldAtomEncoder, sh_lmax = 2. */
+   * mode (ddmi_confidence), OldAtomEncoder, sh_lmax = 2.
+   * With all_atoms = 1: AAOldModel (models/old_aa_model.py), the legacy class on all-atom graphs -- the atom arrays of
+   * ddmi_complex are required as for AAModel, nine OldTensorProductConvLayers per interaction layer under the state-dict keys
+   * conv_layers.{9l + k}, num_confidence_outputs confidence outputs; both modes, ddmi_sample and ddmi_set_crop_cutoff included. */
   int32_t old_model;
   /* confidence-mode options of the new classes (cg_model.py:184-207, aa_model.py:177-211): per-atom predictor in front of the
    * graph mean (`atom_confidence_loss_weight > 0`, atom_num_confidence_outputs = len(atom_rmsd_classification_cutoff) + 1)
@@ -366,6 +369,15 @@ int ddmi_wigner_3j(int l1, int l2, int l3, double* host_out);
  * Replaces torch.normal at utils/sampling.py:140-154 when the caller supplies no draws. */
 int ddmi_debug_philox(const uint32_t* counters, const uint32_t* keys, int n, uint32_t* host_out);
 int ddmi_debug_normal(uint64_t seed, int64_t sample0, int n_samples, int step, int n_comp, float* dev_out, ddmi_stream stream);
+/* The node update of the legacy all-atom class (k_reduce_bn_sum), exposed for tests.  All pointers are device pointers, node tables
+ * and message rows have the library's row stride of 160 floats:
+ *   x_out[i] = pad(x_in[i][:d_in]) + sum over g < n_groups of BN_g(mean of msg rows [toff[g][i], toff[g][i + 1])),  i < n_nodes,
+ * toff int32 [n_groups][n_nodes + 1], bn_mean / bn_scale / bn_bias float [n_groups][d_out] (v -> (v - mean) * scale + bias).
+ * ref_out (optional, n_groups == 1): the same rows from the joint node update of the other classes (k_reduce_bn with the residual),
+ * which one group through this kernel equals bit for bit. */
+int ddmi_debug_reduce_bn_sum(int n_groups, int n_nodes, int d_in, int d_out, const int32_t* toff, const float* msg, const float* bn_mean,
+                             const float* bn_scale, const float* bn_bias, const float* x_in, float* x_out, float* ref_out,
+                             ddmi_stream stream);
 /* Name / duration table of the kernels launched by the last ddmi_forward when timing is on.  enabled: 0 = off, 1 = one row per
  * kernel name, 2 = k_conv_fused split per edge group, 3 = per (layer, edge group). */
 int ddmi_set_kernel_timing(ddmi_model* m, int enabled);
