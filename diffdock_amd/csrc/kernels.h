@@ -393,4 +393,17 @@ struct RandomizeArgs {
 };
 void launch_randomize_position(const RandomizeArgs& a, int maxNl, hipStream_t s);
 
+// ddmi_pose_metrics (k_metrics.hip): pos [P][n][3], ref [K][m][3], perm [S][m] or nullptr (identity, S = 1), atom_index [m] or nullptr
+// (0..m-1, m = n), points [Q][3] or nullptr.  C = cdiv(S, MET_CHUNK) permutation chunks; scratch part_key [P][K][C] (float bits of
+// the smallest sum of the chunk << 32 | its s), part_plain / part_cd [P][K] (identity sum, centroid distance).  Outputs: nullptr =
+// not wanted.  Molecules of up to MET_LDS_ATOMS kept atoms are staged in LDS, larger ones are read in place.
+constexpr int MET_CHUNK = 64, MET_LDS_ATOMS = 2048;
+struct PoseMetricsArgs {
+  const float *pos, *ref; const int *perm, *atom_index; const float* points;
+  int P, n, m, K, S, Q, C;
+  unsigned long long* part_key; float *part_plain, *part_cd;
+  float *rmsd, *rmsd_per_ref, *rmsd_plain, *centroid, *min_self, *min_point; int* best;
+};
+void launch_pose_metrics(const PoseMetricsArgs& a, hipStream_t s);
+
 }  // namespace ddmi

@@ -156,6 +156,31 @@ void randomize_position(Model& m, float* lig_pos, const ddmi_randomize_cfg& rc, 
   launch_randomize_position(a, c.layout ? c.maxNl : c.Nl_one, s);
 }
 
+// The scratch (per (pose, reference): one 64-bit word per chunk of permutations, the identity sum, the centroid distance) belongs to
+// the handle and only grows: a call that needs more than any call before it allocates (hipFree waits for the device, so kernels of an
+// earlier call still in flight keep their memory); every other call enqueues two kernels and returns.
+void pose_metrics(Model& m, const ddmi_pose_metrics_cfg& mc, hipStream_t s) {
+  PoseMetricsArgs a{};
+  a.pos = mc.pos; a.ref = mc.ref; a.perm = mc.perm; a.atom_index = mc.atom_index; a.points = mc.points;
+  a.P = mc.n_poses; a.n = mc.n_atoms; a.m = mc.n_kept; a.K = mc.n_refs; a.S = mc.perm ? mc.n_perms : 1; a.Q = mc.points ? mc.n_points : 0;
+  a.C = cdiv(a.S, MET_CHUNK);
+  DDMI_REQUIRE((long)a.K * a.C <= (1L << 30), DDMI_ERR_CAPACITY, "ddmi_pose_metrics: n_refs * ceil(n_perms / 64) exceeds 2^30");
+  const size_t pk = (size_t)a.P * a.K, key_bytes = round_up((long)(pk * a.C * sizeof(unsigned long long)), 256);
+  const size_t bytes = key_bytes + 2 * pk * sizeof(float);
+  if (bytes > m.metrics_ws_bytes) {
+    m.mpool.release();
+    m.metrics_ws = nullptr; m.metrics_ws_bytes = 0;
+    m.metrics_ws = m.mpool.alloc_bytes(bytes);
+    m.metrics_ws_bytes = bytes;
+  }
+  a.part_key = reinterpret_cast<unsigned long long*>(m.metrics_ws);
+  a.part_plain = reinterpret_cast<float*>(reinterpret_cast<char*>(m.metrics_ws) + key_bytes);
+  a.part_cd = a.part_plain + pk;
+  a.rmsd = mc.rmsd; a.best = mc.best; a.rmsd_per_ref = mc.rmsd_per_ref; a.rmsd_plain = mc.rmsd_plain;
+  a.centroid = mc.centroid_distance; a.min_self = mc.min_self_distance; a.min_point = mc.min_point_distance;
+  launch_pose_metrics(a, s);
+}
+
 void sample(Model& m, float* lig_pos, const ddmi_sample_cfg& sc, hipStream_t s) {
   DDMI_REQUIRE(m.has_complex, DDMI_ERR_STATE, "ddmi_set_complex must precede ddmi_sample");
   check_sample_cfg(m, sc);

@@ -384,6 +384,52 @@ class MIScoreModel:
                 t.record_stream(torch.cuda.current_stream(dev))
         return pos
 
+    def pose_metrics(self, pos, ref, perm=None, atom_index=None, points=None, per_ref=False):
+        """Judge poses on the device (ddmi_pose_metrics; evaluate.py:474-505): `pos` [P, n, 3] or a trajectory [T, P, n, 3], `ref`
+        [K, m, 3] (or [m, 3]) known poses, `perm` int [S, m] graph isomorphisms as metrics.isomorphisms returns them (None = the
+        identity), `atom_index` int [m] the atoms of a pose that are compared, in the order of `ref` (None = all n; the reference's
+        filterHs), `points` [Q, 3] anything to keep clear of.  Returns a dict of device tensors with the leading shape of `pos`:
+        rmsd (symmetry-corrected, min over references), best [.., 2] int32 (the reference and the row of perm attaining it; ties go
+        to the lowest), rmsd_plain (identity only), centroid_distance, min_self_distance (+inf for one atom), min_point_distance
+        (+inf without points), and with per_ref rmsd_per_ref [.., K].  The call needs no complex and does not synchronise."""
+        dev = self.device
+        pos = torch.as_tensor(pos).to(dev, torch.float32).contiguous()
+        if pos.dim() not in (3, 4) or pos.shape[-1] != 3:
+            raise ValueError(f"pos: [P, n, 3] or [T, P, n, 3] expected, got {tuple(pos.shape)}")
+        lead, n = tuple(pos.shape[:-2]), pos.shape[-2]
+        ref = torch.as_tensor(ref).to(dev, torch.float32).contiguous()
+        ref = ref.unsqueeze(0) if ref.dim() == 2 else ref
+        i32 = lambda t: None if t is None else torch.as_tensor(t).to(dev, torch.int32).contiguous()
+        perm, atom_index = i32(perm), i32(atom_index)
+        m = n if atom_index is None else atom_index.numel()
+        if ref.dim() != 3 or tuple(ref.shape[1:]) != (m, 3):
+            raise ValueError(f"ref: [K, {m}, 3] expected, got {tuple(ref.shape)}")
+        if perm is not None and (perm.dim() != 2 or perm.shape[1] != m):
+            raise ValueError(f"perm: [S, {m}] expected, got {tuple(perm.shape)}")
+        if points is not None:
+            points = torch.as_tensor(points).to(dev, torch.float32).reshape(-1, 3).contiguous()
+            points = points if points.numel() else None
+        P, K = int(np.prod(lead)), ref.shape[0]
+        f = lambda *shape, dtype=torch.float32: torch.empty(lead + shape, dtype=dtype, device=dev)
+        out = dict(rmsd=f(), best=f(2, dtype=torch.int32), rmsd_plain=f(), centroid_distance=f(), min_self_distance=f(),
+                   min_point_distance=f())
+        if per_ref:
+            out["rmsd_per_ref"] = f(K)
+        mc = _lib.PoseMetricsCfg()
+        mc.struct_size = C.sizeof(_lib.PoseMetricsCfg)
+        mc.n_poses, mc.n_atoms, mc.n_kept, mc.n_refs = P, n, m, K
+        mc.n_perms = 0 if perm is None else perm.shape[0]
+        mc.n_points = 0 if points is None else points.shape[0]
+        inputs = dict(pos=pos, ref=ref, perm=perm, atom_index=atom_index, points=points)
+        for name, t in list(inputs.items()) + list(out.items()):
+            setattr(mc, name, None if t is None else t.data_ptr())
+        _lib.check(self.lib, self.lib.ddmi_pose_metrics(self._h, C.byref(mc), self._stream()))
+        if dev.type == "cuda":   # converted copies of the inputs must outlive the enqueued kernels
+            for t in inputs.values():
+                if t is not None:
+                    t.record_stream(torch.cuda.current_stream(dev))
+        return out
+
     def _sample_cfg(self, inference_steps, schedules, noise, seed, sample_ids, ode, no_random, no_final_step_noise,
                     temp_sampling, temp_psi, temp_sigma_data, crop_beyond):
         """ddmi_sample_cfg + the host / device arrays it points into (returned so that they outlive the call)."""

@@ -356,6 +356,45 @@ typedef struct ddmi_randomize_cfg {
 } ddmi_randomize_cfg;
 int ddmi_randomize_position(ddmi_model* m, float* lig_pos, const ddmi_randomize_cfg* cfg, ddmi_stream stream);
 
+/* Judging sampled poses on the device -- what evaluate.py:474-505, utils/training.py:282-287 (inference_epoch_fix) and
+ * confidence/dataset.py:241 compute on the host from the final poses: the symmetry-corrected RMSD to the known pose(s), the
+ * uncorrected RMSD, the centroid distance and the minimum intra-ligand distance, plus the minimum distance to a point set.
+ * The handle gives the device, the stream order and the error text only: no complex, weights or tables are needed, so the poses
+ * may be final poses [N] as well as a recorded trajectory [steps * N] (ddmi_sample_record.pos).  Two kernels are enqueued and the
+ * call returns; there is no host synchronisation (a call larger than any before it on the handle allocates its scratch first).
+ * One wave owns the sum of one (pose, reference, permutation) and reduces it in a fixed order, so every value is bit-identical
+ * whatever the other poses, references and permutations of the call are; every min is deterministic.
+ * m-space: atom j of a pose is pos[p][atom_index[j]] (the kept atoms in order, the reference's filterHs of evaluate.py:414 and
+ * :430-431); ref and perm live in m-space.  A row of perm is one graph isomorphism as spyrmsd enumerates them: the pair
+ * (idx1, idx2) of spyrmsd/rmsd.py:184-187 is the row perm[idx2[i]] = idx1[i].  Entries of perm and atom_index outside their range
+ * are clamped into it.  All arrays are device memory; every output is optional (NULL = not computed).
+ * DDMI_ERR_ARG: struct_size mismatch, NULL pos or ref, n_poses / n_atoms / n_kept / n_refs < 1, n_kept > n_atoms, n_kept != n_atoms
+ * without atom_index, perm with n_perms < 1, points with n_points < 1.  DDMI_ERR_CAPACITY: n_refs * ceil(n_perms / 64) > 2^30. */
+typedef struct ddmi_pose_metrics_cfg {
+  uint32_t struct_size;        /* sizeof of this struct the caller was built against                                        */
+  int32_t n_poses;             /* P: poses (evaluate.py:430 ligand_pos rows; steps * N for a trajectory)                    */
+  int32_t n_atoms;             /* n: atoms of a pose                                                                        */
+  int32_t n_kept;              /* m: atoms compared (evaluate.py:414 filterHs.sum()); = n_atoms without atom_index          */
+  int32_t n_refs;              /* K: known poses (evaluate.py:416-428 orig_ligand_pos rows)                                 */
+  int32_t n_perms;             /* S: rows of perm (len of spyrmsd's isomorphisms, rmsd.py:176); ignored without perm        */
+  int32_t n_points;            /* Q: rows of points; ignored without points                                                 */
+  const float* pos;            /* [P, n, 3]                                                                                 */
+  const float* ref;            /* [K, m, 3]                                                                                 */
+  const int32_t* perm;         /* [S, m] or NULL (identity, S = 1)                                                          */
+  const int32_t* atom_index;   /* [m] or NULL (0..n-1)                                                                      */
+  const float* points;         /* [Q, 3] or NULL: anything to keep clear of (residue or receptor-atom positions)            */
+  float* rmsd;                 /* [P]  sqrt(min over (k, s) of sum_j |ref[k, perm[s, j]] - pos[p, atom_index[j]]|^2 / m):
+                                       spyrmsd/rmsd.py:179-203 with minimize = center = False, np.min of evaluate.py:484    */
+  int32_t* best;               /* [P, 2]  the (k, s) attaining it; ties go to the lowest k * S + s                          */
+  float* rmsd_per_ref;         /* [P, K]  the value before the min over k (evaluate.py:483 rmsds, transposed)               */
+  float* rmsd_plain;           /* [P]  identity permutation only, min over k: the fallback formula of evaluate.py:481       */
+  float* centroid_distance;    /* [P]  evaluate.py:486                                                                      */
+  float* min_self_distance;    /* [P]  evaluate.py:503-505 over the kept atoms; +inf for m = 1                              */
+  float* min_point_distance;   /* [P]  min over j, q of |pos[p, atom_index[j]] - points[q]|; +inf without points.  The
+                                       reference declares min_cross_distances_list (evaluate.py:331) and never fills it     */
+} ddmi_pose_metrics_cfg;
+int ddmi_pose_metrics(ddmi_model* m, const ddmi_pose_metrics_cfg* cfg, ddmi_stream stream);
+
 /* Introspection for tests and profiling: copy a named internal buffer to the host.
  * ddmi_debug_shape returns the element count and up to 4 dims; names are listed in DESIGN.md. */
 int ddmi_debug_shape(ddmi_model* m, const char* name, int64_t shape[4], int* ndim, int* is_int);

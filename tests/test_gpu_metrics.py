@@ -1,0 +1,52 @@
+"""Pose metrics on the MI355X: ddmi_pose_metrics, MIScoreModel.pose_metrics, diffdock_amd.metrics.evaluate_poses.
+Case bodies live in tests/metrics_cases.py (the emulator runs them in tests/test_metrics_emu.py)."""
+import pytest
+import torch
+
+from diffdock_amd.model import MIScoreModel
+from util import tables
+import metrics_cases as M
+
+pytestmark = pytest.mark.gpu
+
+
+def make(cfg, sd):
+    assert torch.cuda.is_available(), "these tests need the MI355X (-m gpu)"
+    m = MIScoreModel(cfg, device="cuda:0")     # raises DdmiError if libddmi.so is not built: no fallback
+    m.load_state_dict(sd)
+    m.set_tables(*tables())
+    return m
+
+
+def place(x):
+    return x.to("cuda:0")
+
+
+@pytest.mark.parametrize("name", ["1a0q", "sym576"])
+def test_fixture_molecules_match_the_executed_spyrmsd(name):
+    M.fixture_case(make, place, name)
+
+
+@pytest.mark.parametrize("shape", M.EDGE_SHAPES)
+def test_edge_shapes(shape):
+    M.edge_shape_case(make, place, shape)
+
+
+def test_atom_index_and_exact_ties_fall_to_the_lowest_index():
+    M.atom_index_ties_case(make, place)
+
+
+def test_values_do_not_depend_on_the_other_poses_references_or_permutations():
+    M.independence_case(make, place)
+
+
+def test_evaluate_poses():
+    M.evaluate_case(make, place)
+
+
+def test_errors():
+    M.errors_case(make, place)
+
+
+def test_recorded_trajectory_through_pose_metrics():
+    M.recorded_trajectory_case(make, place)

@@ -1,0 +1,92 @@
+#!/usr/bin/env python
+"""Time of judging 40 sampled poses: metrics.evaluate_poses on the device against the host route of the reference
+(evaluate.py:474-505: copy the poses back, then spyrmsd's Python loop over all graph isomorphisms for every pose and reference) on
+the 576-isomorphism molecule of tests/golden/pose_metrics.pt.
+
+    python tools/metrics_bench.py [--molecule sym576|1a0q] [--reps R] [--warmup W]
+
+  device  evaluate_poses(pos, ref, perm, confidence): every output of ddmi_pose_metrics plus the ordering, results left on the device;
+          the clock stops after a device synchronisation
+  host    pos.cpu(), then the loop of spyrmsd/rmsd.py:183-203 (one numpy gather, difference and sum per (pose, reference,
+          isomorphism)) and the numpy one-liners of evaluate.py:486 and :503-505 -- spyrmsd.rmsd.symmrmsd itself when the package
+          can be imported, else the restatement below, which the fixture generator checked to be equal to it to the last bit
+
+One JSON line: {"molecule", "poses", "refs", "isomorphisms", "device_ms", "host_ms", "speedup", "host_arm"} (medians).  Information
+only: nothing in the suite depends on these numbers."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from diffdock_amd.config import TINY  # noqa: E402
+from diffdock_amd.metrics import evaluate_poses  # noqa: E402
+from diffdock_amd.model import MIScoreModel  # noqa: E402
+
+
+def host_loop(ref, poses, perm):
+    """min over isomorphisms of the squared displacement, per pose, as a Python loop (spyrmsd/rmsd.py:183-203, minimize=False)."""
+    out = []
+    for c in poses:
+        best = np.inf
+        for row in perm:
+            best = min(best, np.sum((ref[row] - c) ** 2))
+        out.append(np.sqrt(best / len(c)))
+    return np.array(out)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--molecule", default="sym576")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=1)
+    args = ap.parse_args()
+    mol = torch.load(os.path.join(ROOT, "tests", "golden", "pose_metrics.pt"), weights_only=False)[args.molecule]
+    m = MIScoreModel(TINY, device="cuda:0")          # pose metrics need a handle only: no weights, tables or complex
+    pos, ref, perm = mol["pos"].to("cuda:0"), mol["ref"].to("cuda:0"), mol["perm"].to("cuda:0")
+    conf = torch.linspace(0, 1, pos.shape[0], device="cuda:0")
+    try:
+        from spyrmsd.rmsd import symmrmsd
+        z, A = mol["z"].numpy(), mol["adjacency"].numpy()
+        host_rmsd, arm = (lambda r, p: np.asarray(symmrmsd(r, list(p), z, z, A, A))), "spyrmsd.rmsd.symmrmsd"
+    except ImportError:
+        rows = mol["perm"].numpy()
+        host_rmsd, arm = (lambda r, p: host_loop(r, p, rows)), "restated loop"
+
+    def device():
+        out = evaluate_poses(pos, ref, model=m, perm=perm, confidence=conf)
+        torch.cuda.synchronize()
+        return out["rmsd"]
+
+    def host():
+        p, r = pos.cpu().numpy().astype(np.float64), ref.cpu().numpy().astype(np.float64)
+        rmsd = np.min(np.asarray([host_rmsd(r[k], p) for k in range(len(r))]), axis=0)
+        np.min(np.linalg.norm(p.mean(axis=1)[None, :] - r.mean(axis=1)[:, None], axis=2), axis=0)
+        d = np.linalg.norm(p[:, :, None, :] - p[:, None, :, :], axis=-1)
+        np.min(np.where(np.eye(d.shape[2]), np.inf, d), axis=(1, 2))
+        return rmsd
+
+    def timed(fn):
+        for _ in range(args.warmup):
+            fn()
+        ts = []
+        for _ in range(args.reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fn()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return statistics.median(ts), out
+    (d_ms, d_out), (h_ms, h_out) = timed(device), timed(host)
+    assert np.abs(d_out.cpu().numpy() / h_out - 1).max() < 1e-5
+    print(json.dumps({"molecule": args.molecule, "poses": int(pos.shape[0]), "refs": int(ref.shape[0]), "isomorphisms": int(perm.shape[0]),
+                      "device_ms": round(d_ms, 3), "host_ms": round(h_ms, 2), "speedup": round(h_ms / d_ms, 1), "host_arm": arm}))
+
+
+if __name__ == "__main__":
+    main()
