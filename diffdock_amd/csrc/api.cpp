@@ -243,6 +243,21 @@ int ddmi_pose_metrics(ddmi_model* h, const ddmi_pose_metrics_cfg* cfg, ddmi_stre
   });
 }
 
+int ddmi_pose_fit(ddmi_model* h, const ddmi_pose_fit_cfg* cfg, ddmi_stream s) {
+  return guard([&] {
+    DDMI_REQUIRE(h && cfg, DDMI_ERR_ARG, "null argument");
+    DDMI_REQUIRE(cfg->struct_size == sizeof(ddmi_pose_fit_cfg), DDMI_ERR_ARG, "ddmi_pose_fit_cfg.struct_size does not match this library");
+    DDMI_REQUIRE(cfg->pos && cfg->ref, DDMI_ERR_ARG, "ddmi_pose_fit_cfg: pos and ref are required");
+    DDMI_REQUIRE(cfg->n_poses > 0 && cfg->n_atoms > 0 && cfg->n_kept > 0 && cfg->n_refs > 0, DDMI_ERR_ARG,
+                 "ddmi_pose_fit_cfg: n_poses, n_atoms, n_kept and n_refs must be positive");
+    DDMI_REQUIRE(cfg->n_kept <= cfg->n_atoms, DDMI_ERR_ARG, "ddmi_pose_fit_cfg: n_kept > n_atoms");
+    DDMI_REQUIRE(cfg->atom_index || cfg->n_kept == cfg->n_atoms, DDMI_ERR_ARG, "ddmi_pose_fit_cfg: without atom_index n_kept must equal n_atoms");
+    DDMI_REQUIRE(!cfg->perm || cfg->n_perms >= 1, DDMI_ERR_ARG, "ddmi_pose_fit_cfg: perm given with n_perms < 1");
+    DDMI_CHECK_HIP(hipSetDevice(h->m.device));
+    pose_fit(h->m, *cfg, (hipStream_t)s);
+  });
+}
+
 int ddmi_set_sample_record(ddmi_model* h, const ddmi_sample_record* r) {
   return guard([&] {
     DDMI_REQUIRE(h, DDMI_ERR_ARG, "null model");

@@ -16,6 +16,7 @@
 // Molecules whose kept atoms do not fit the LDS budget (m > MET_LDS_ATOMS) run the same arithmetic in the same order on global memory.
 #include <algorithm>
 
+#include "jacobi4.h"
 #include "kernels.h"
 
 namespace ddmi {
@@ -204,6 +205,184 @@ void launch_pose_metrics(const PoseMetricsArgs& a, hipStream_t s) {
   }
   if (staged) hipLaunchKernelGGL(k_pose_finish<true>, dim3(a.P), dim3(64 * MET_WAVES), smem2, s, a);
   else hipLaunchKernelGGL(k_pose_finish<false>, dim3(a.P), dim3(64 * MET_WAVES), smem2, s, a);
+  DDMI_CHECK_HIP(hipGetLastError());
+}
+
+// ------------------------------------------------------------------ ddmi_pose_fit
+// The minimised symmetric RMSD (spyrmsd.rmsd.symmrmsd with minimize = True, spyrmsd/rmsd.py:179-203 and spyrmsd/qcp.py: for every
+// graph isomorphism the RMSD after the optimal rigid superposition, then the min) and the transform that attains it.  For pose p,
+// reference k, permutation s, with a_j = pos[p, atom_index[j]] and b_j = ref[k, perm[s, j]]:
+//   ca = mean a_j, cb = mean b_j, Ga = sum |a_j - ca|^2, Gb = sum |b_j - cb|^2, M = sum (a_j - ca)(b_j - cb)^T,
+//   lambda = the largest eigenvalue of Horn's key matrix of M, e = Ga + Gb - 2 lambda,
+//   rmsd_min = 0 where |e| < 1e-9 (the reference's atol, qcp.py:283), else sqrt(max(e, 0) / m).
+// ALL of it is float64 on the float32 inputs: e is a difference of numbers of size m r^2 and is m rmsd^2, which float32 cannot hold
+// for a near-perfect conformer.  lambda comes from the cyclic Jacobi of jacobi4.h, which needs no special case where the largest
+// eigenvalue is degenerate (m = 2, collinear atoms); the characteristic-polynomial Newton of QCP is not used.
+// Two launches with the decomposition and the properties of the kernels above -- no atomics, no host synchronisation, scratch from
+// the handle's growing pool, and the value of a triple depends on its own inputs only:
+//   k_pose_fit_sums    one workgroup (4 waves) per (p, k, chunk of MET_CHUNK permutations), atoms staged in LDS as float32 or read in
+//                      place as above.  Wave 0 computes (ca, Ga) and wave 1 (cb, Gb) before the loop: lane l adds the atoms l, l + 64,
+//                      .. in order, then the fixed butterfly of wave_sum_f64 -- a function of the pose (the reference) alone, whatever
+//                      P, K, S or the grid are.  ONE WAVE owns a triple: nine explicit-fma sums in the same lane order and the same
+//                      butterfly; the sums of the wave's i-th triple stay in lane i, and the eigenvalues of its (up to 16) triples
+//                      are found together, one lane each.  The chunk minimum is taken on (float bits of (float) e << 32 | s)
+//                      with e clamped as above: rounding to float32 is monotone, so this is the rounding of the float64 minimum; equal
+//                      keys fall to the lowest s and a NaN loses.
+//   k_pose_fit_finish  one workgroup (one wave) per pose: min over the chunks, then over k ascending with a strict `<`; then M again for
+//                      the winning (k, s), the dominant eigenvector q of its key matrix, the proper rotation R(q) (det = +1: QCP never
+//                      reflects) and t = cb - R ca, so that R a_j + t ~ b_j; R and t are stored as float32.  m = 1 gives the identity.
+//                      Where the largest eigenvalue is degenerate (m = 2, collinear atoms: any rotation about the common axis) every
+//                      maximiser is a correct answer and the one returned is the one the Jacobi sweeps arrive at.
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
+    const unsigned hi = (unsigned)__shfl_xor((int)(unsigned)(b >> 32), m, 64), lo = (unsigned)__shfl_xor((int)(unsigned)b, m, 64);
+    v += __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+  }
+  return v;
+}
+
+// one wave: c[0..2] = the centroid of the m atoms atom(j), c[3] = sum_j |atom(j) - centroid|^2
+template <class Atom> __device__ __forceinline__ void fit_center(const Atom& atom, int m, int lane, double* c) {
+  double sx = 0.0, sy = 0.0, sz = 0.0;
+  for (int j = lane; j < m; j += 64) {
+    float x, y, z;
+    atom(j, x, y, z);
+    sx += (double)x; sy += (double)y; sz += (double)z;
+  }
+  const double cx = wave_sum_f64(sx) / (double)m, cy = wave_sum_f64(sy) / (double)m, cz = wave_sum_f64(sz) / (double)m;
+  double g = 0.0;
+  for (int j = lane; j < m; j += 64) {
+    float x, y, z;
+    atom(j, x, y, z);
+    const double dx = (double)x - cx, dy = (double)y - cy, dz = (double)z - cz;
+    g = fma(dz, dz, fma(dy, dy, fma(dx, dx, g)));
+  }
+  c[0] = cx; c[1] = cy; c[2] = cz; c[3] = wave_sum_f64(g);
+}
+// one wave: M [3][3] = sum_j (a_j - ca)(b_j - cb)^T with b_j = the reference atom pr[j] (pr == nullptr: j)
+template <bool STAGED> __device__ __forceinline__ void fit_cross(const MetView<STAGED>& v, const int* __restrict__ pr, int m, int lane,
+                                                                 const double* ca, const double* cb, double* M) {
+  for (int i = 0; i < 9; ++i) M[i] = 0.0;
+  for (int j = lane; j < m; j += 64) {
+    float px, py, pz, qx, qy, qz;
+    v.pose(j, px, py, pz);
+    v.refr(pr ? met_clamp(pr[j], m) : j, qx, qy, qz);
+    const double ax = (double)px - ca[0], ay = (double)py - ca[1], az = (double)pz - ca[2];
+    const double bx = (double)qx - cb[0], by = (double)qy - cb[1], bz = (double)qz - cb[2];
+    M[0] = fma(ax, bx, M[0]); M[1] = fma(ax, by, M[1]); M[2] = fma(ax, bz, M[2]);
+    M[3] = fma(ay, bx, M[3]); M[4] = fma(ay, by, M[4]); M[5] = fma(ay, bz, M[5]);
+    M[6] = fma(az, bx, M[6]); M[7] = fma(az, by, M[7]); M[8] = fma(az, bz, M[8]);
+  }
+  for (int i = 0; i < 9; ++i) M[i] = wave_sum_f64(M[i]);
+}
+
+// smem: MET_WAVES 64-bit words, 8 doubles (ca, Ga, cb, Gb), then (STAGED) 6 m floats.
+template <bool STAGED> __global__ __launch_bounds__(64 * MET_WAVES) void k_pose_fit_sums(PoseFitArgs a, int p0) {
+  DDMI_DYN_SMEM(unsigned long long, wk);
+  double* cen = reinterpret_cast<double*>(wk + MET_WAVES);
+  float* xs = reinterpret_cast<float*>(cen + 8);
+  float* rs = xs + 3 * (size_t)a.m;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int c = (int)(blockIdx.x % (unsigned)a.C), k = (int)((blockIdx.x / (unsigned)a.C) % (unsigned)a.K);
+  const int p = p0 + (int)(blockIdx.x / ((unsigned)a.C * (unsigned)a.K));
+  const int m = a.m;
+  const float* __restrict__ pos = a.pos + (size_t)p * a.n * 3;
+  const float* __restrict__ ref = a.ref + (size_t)k * m * 3;
+  MetView<STAGED> v{STAGED ? xs : pos, STAGED ? rs : ref, a.atom_index, a.n};
+  if (STAGED) {
+    for (int j = tid; j < m; j += 64 * MET_WAVES) {
+      const int at = a.atom_index ? met_clamp(a.atom_index[j], a.n) : j;
+      for (int d = 0; d < 3; ++d) { xs[3 * j + d] = pos[3 * (size_t)at + d]; rs[3 * j + d] = ref[3 * (size_t)j + d]; }
+    }
+    __syncthreads();
+  }
+  if (w < 2) {   // wave-uniform
+    double cc[4];
+    if (w == 0) fit_center([&](int j, float& x, float& y, float& z) { v.pose(j, x, y, z); }, m, lane, cc);
+    else fit_center([&](int j, float& x, float& y, float& z) { v.refr(j, x, y, z); }, m, lane, cc);
+    if (lane == 0) { cen[4 * w] = cc[0]; cen[4 * w + 1] = cc[1]; cen[4 * w + 2] = cc[2]; cen[4 * w + 3] = cc[3]; }
+  }
+  __syncthreads();
+  double ca[3] = {cen[0], cen[1], cen[2]}, cb[3] = {cen[4], cen[5], cen[6]};
+  const double G = cen[3] + cen[7];
+  const int s_lo = c * MET_CHUNK, s_hi = a.S - s_lo > MET_CHUNK ? s_lo + MET_CHUNK : a.S;
+  // The wave's triples s = s_lo + w + MET_WAVES i, i < MET_CHUNK / MET_WAVES <= 64: the sums of triple i are left in lane i, and the
+  // eigenvalues of all of them are then found at once, one lane each -- the same instructions on the same sums in whichever lane.
+  static_assert(MET_CHUNK <= 64 * MET_WAVES, "one lane per triple of a wave");
+  double M[9], mine[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  int i = 0;
+  for (int s = s_lo + w; s < s_hi; s += MET_WAVES, ++i) {   // wave-uniform: every lane of the wave takes part in the butterflies
+    fit_cross<STAGED>(v, a.perm ? a.perm + (size_t)s * m : nullptr, m, lane, ca, cb, M);
+    for (int j = 0; j < 9; ++j) mine[j] = lane == i ? M[j] : mine[j];
+  }
+  unsigned long long best = ~0ull;
+  if (lane < i) {
+    double N[16], q[4];
+    horn_key_matrix(mine, N);
+    double e = G - 2.0 * max_eigvec4(N, q);
+    e = fabs(e) < 1e-9 ? 0.0 : (e < 0.0 ? 0.0 : e);   // (a NaN stays a NaN)
+    best = ((unsigned long long)__float_as_uint((float)e) << 32) | (unsigned)(s_lo + w + MET_WAVES * lane);
+  }
+  best = wave_min_u64(best);
+  if (lane == 0) wk[w] = best;
+  __syncthreads();
+  if (tid == 0) {
+    unsigned long long b = wk[0];
+    for (int i = 1; i < MET_WAVES; ++i) b = wk[i] < b ? wk[i] : b;
+    a.part_key[((size_t)p * a.K + k) * a.C + c] = b;
+  }
+}
+
+__global__ __launch_bounds__(64) void k_pose_fit_finish(PoseFitArgs a) {
+  const int p = blockIdx.x, lane = threadIdx.x;
+  const int m = a.m, K = a.K, C = a.C;
+  unsigned bv = 0xffffffffu, bs = 0; int bk = 0;   // (the same in every lane: wave_min_u64 leaves the minimum in all of them)
+  for (int k = 0; k < K; ++k) {
+    const unsigned long long* __restrict__ pk = a.part_key + ((size_t)p * K + k) * C;
+    unsigned long long key = ~0ull;
+    for (int c = lane; c < C; c += 64) key = pk[c] < key ? pk[c] : key;
+    key = wave_min_u64(key);
+    const unsigned val = (unsigned)(key >> 32);
+    if (lane == 0 && a.rmsd_min_per_ref) a.rmsd_min_per_ref[(size_t)p * K + k] = sqrtf(__uint_as_float(val) / (float)m);
+    if (val < bv) { bv = val; bs = (unsigned)key; bk = k; }
+  }
+  if (lane == 0) {
+    if (a.rmsd_min) a.rmsd_min[p] = sqrtf(__uint_as_float(bv) / (float)m);
+    if (a.best_min) { a.best_min[2 * (size_t)p] = bk; a.best_min[2 * (size_t)p + 1] = (int)bs; }
+  }
+  if (!a.rotation && !a.translation) return;
+  const int s = met_clamp((int)bs, a.S);
+  MetView<false> v{a.pos + (size_t)p * a.n * 3, a.ref + (size_t)bk * m * 3, a.atom_index, a.n};
+  double ca[4], cb[4], M[9];
+  fit_center([&](int j, float& x, float& y, float& z) { v.pose(j, x, y, z); }, m, lane, ca);
+  fit_center([&](int j, float& x, float& y, float& z) { v.refr(j, x, y, z); }, m, lane, cb);
+  fit_cross<false>(v, a.perm ? a.perm + (size_t)s * m : nullptr, m, lane, ca, cb, M);
+  if (lane == 0) {
+    double N[16], q[4], R[9];
+    horn_key_matrix(M, N);
+    max_eigvec4(N, q);
+    quat_rotation(q, R);
+    if (a.rotation) for (int i = 0; i < 9; ++i) a.rotation[9 * (size_t)p + i] = (float)R[i];
+    if (a.translation)
+      for (int i = 0; i < 3; ++i) a.translation[3 * (size_t)p + i] = (float)(cb[i] - (R[3 * i] * ca[0] + R[3 * i + 1] * ca[1] + R[3 * i + 2] * ca[2]));
+  }
+}
+
+void launch_pose_fit(const PoseFitArgs& a, hipStream_t s) {
+  if (a.P <= 0) return;
+  const bool staged = a.m <= MET_LDS_ATOMS;
+  const size_t smem = MET_WAVES * sizeof(unsigned long long) + 8 * sizeof(double) + (staged ? 6 * (size_t)a.m * sizeof(float) : 0);
+  const long per_pose = (long)a.K * a.C;
+  const int step = (int)std::max(1L, std::min((long)a.P, (1L << 30) / per_pose));   // poses per launch: the grid stays below 2^31
+  for (int p0 = 0; p0 < a.P; p0 += step) {
+    const unsigned grid = (unsigned)(per_pose * std::min(step, a.P - p0));
+    if (staged) hipLaunchKernelGGL(k_pose_fit_sums<true>, dim3(grid), dim3(64 * MET_WAVES), smem, s, a, p0);
+    else hipLaunchKernelGGL(k_pose_fit_sums<false>, dim3(grid), dim3(64 * MET_WAVES), smem, s, a, p0);
+    DDMI_CHECK_HIP(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_pose_fit_finish, dim3(a.P), dim3(64), 0, s, a);
   DDMI_CHECK_HIP(hipGetLastError());
 }
 

@@ -8,6 +8,7 @@
 //                       (utils/geometry.py:246-276).  The optimal proper rotation is obtained
 //                       from Horn's quaternion eigenproblem (float64 Jacobi) instead of an SVD
 //                       with reflection fix: the same minimiser, no 3x3 SVD kernel needed.
+#include "jacobi4.h"
 #include "kernels.h"
 
 namespace ddmi {
@@ -215,43 +216,6 @@ __device__ __forceinline__ void axis_angle_to_matrix(float ax, float ay, float a
   R[0] = 1 - two_s * (j * j + k * k); R[1] = two_s * (i * j - k * r); R[2] = two_s * (i * k + j * r);
   R[3] = two_s * (i * j + k * r); R[4] = 1 - two_s * (i * i + k * k); R[5] = two_s * (j * k - i * r);
   R[6] = two_s * (i * k - j * r); R[7] = two_s * (j * k + i * r); R[8] = 1 - two_s * (i * i + j * j);
-}
-
-// dominant eigenvector of a symmetric 4x4 (cyclic Jacobi, float64)
-__device__ void max_eigvec4(double* A, double* q) {
-  double V[16];
-  for (int i = 0; i < 16; ++i) V[i] = (i % 5 == 0) ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 30; ++sweep) {
-    double off = 0;
-    for (int p = 0; p < 4; ++p) for (int r = p + 1; r < 4; ++r) off += A[p * 4 + r] * A[p * 4 + r];
-    if (off < 1e-30) break;
-    for (int p = 0; p < 3; ++p)
-      for (int r = p + 1; r < 4; ++r) {
-        const double apr = A[p * 4 + r];
-        if (fabs(apr) < 1e-300) continue;
-        const double theta = (A[r * 4 + r] - A[p * 4 + p]) / (2.0 * apr);
-        const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-        for (int k = 0; k < 4; ++k) {
-          const double akp = A[k * 4 + p], akr = A[k * 4 + r];
-          A[k * 4 + p] = c * akp - s * akr;
-          A[k * 4 + r] = s * akp + c * akr;
-        }
-        for (int k = 0; k < 4; ++k) {
-          const double apk = A[p * 4 + k], ark = A[r * 4 + k];
-          A[p * 4 + k] = c * apk - s * ark;
-          A[r * 4 + k] = s * apk + c * ark;
-        }
-        for (int k = 0; k < 4; ++k) {
-          const double vkp = V[k * 4 + p], vkr = V[k * 4 + r];
-          V[k * 4 + p] = c * vkp - s * vkr;
-          V[k * 4 + r] = s * vkp + c * vkr;
-        }
-      }
-  }
-  int best = 0;
-  for (int i = 1; i < 4; ++i) if (A[i * 4 + i] > A[best * 4 + best]) best = i;
-  for (int k = 0; k < 4; ++k) q[k] = V[k * 4 + best];
 }
 
 // one graph (64 threads): p [Nl][3] in place; tr / rot [3] and tor [R] (or nullptr) are the graph's updates, rot_u / rot_v

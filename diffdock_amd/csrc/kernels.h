@@ -406,4 +406,15 @@ struct PoseMetricsArgs {
 };
 void launch_pose_metrics(const PoseMetricsArgs& a, hipStream_t s);
 
+// ddmi_pose_fit (k_metrics.hip): the inputs of PoseMetricsArgs without points, in the same m-space.  Scratch part_key [P][K][C]: float
+// bits of the smallest clamped residual e = Ga + Gb - 2 lambda of the chunk << 32 | its s.  Outputs: nullptr = not wanted; rotation
+// [P][3][3] row-major and translation [P][3] move the kept atoms of pose p onto ref[k, perm[s]] at best_min[p] = (k, s).
+struct PoseFitArgs {
+  const float *pos, *ref; const int *perm, *atom_index;
+  int P, n, m, K, S, C;
+  unsigned long long* part_key;
+  float *rmsd_min, *rmsd_min_per_ref, *rotation, *translation; int* best_min;
+};
+void launch_pose_fit(const PoseFitArgs& a, hipStream_t s);
+
 }  // namespace ddmi

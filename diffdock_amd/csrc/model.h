@@ -138,7 +138,7 @@ struct Model {
   bool uniform_t = false;   // the forward in flight has one t for every graph of the batch (set by the device step loop, sample())
   double crop_cutoff = 0.0;  // > 0: receptor cropped to this distance from the ligand in ddmi_forward (crop_beyond)
   DevicePool cpool;
-  DevicePool mpool; void* metrics_ws = nullptr; size_t metrics_ws_bytes = 0;   // ddmi_pose_metrics scratch: grows, never shrinks
+  DevicePool mpool; void* metrics_ws = nullptr; size_t metrics_ws_bytes = 0;   // ddmi_pose_metrics / ddmi_pose_fit scratch: grows, never shrinks
   struct Cx;  // cx.h
   std::shared_ptr<Cx> cx;
   std::map<std::string, DebugEntry> debug;
@@ -183,5 +183,6 @@ void perturb(Model& m, float* tr, float* rot, float* tor, const ddmi_sample_cfg&
 void randomize_position(Model& m, float* lig_pos, const ddmi_randomize_cfg& rc, hipStream_t s);
 // RMSDs and clearances of poses against reference poses (evaluate.py:474-505); needs no complex
 void pose_metrics(Model& m, const ddmi_pose_metrics_cfg& mc, hipStream_t s);
+void pose_fit(Model& m, const ddmi_pose_fit_cfg& fc, hipStream_t s);
 
 }  // namespace ddmi

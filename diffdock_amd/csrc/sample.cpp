@@ -159,6 +159,14 @@ void randomize_position(Model& m, float* lig_pos, const ddmi_randomize_cfg& rc, 
 // The scratch (per (pose, reference): one 64-bit word per chunk of permutations, the identity sum, the centroid distance) belongs to
 // the handle and only grows: a call that needs more than any call before it allocates (hipFree waits for the device, so kernels of an
 // earlier call still in flight keep their memory); every other call enqueues two kernels and returns.
+static void metrics_scratch(Model& m, size_t bytes) {
+  if (bytes <= m.metrics_ws_bytes) return;
+  m.mpool.release();
+  m.metrics_ws = nullptr; m.metrics_ws_bytes = 0;
+  m.metrics_ws = m.mpool.alloc_bytes(bytes);
+  m.metrics_ws_bytes = bytes;
+}
+
 void pose_metrics(Model& m, const ddmi_pose_metrics_cfg& mc, hipStream_t s) {
   PoseMetricsArgs a{};
   a.pos = mc.pos; a.ref = mc.ref; a.perm = mc.perm; a.atom_index = mc.atom_index; a.points = mc.points;
@@ -167,18 +175,27 @@ void pose_metrics(Model& m, const ddmi_pose_metrics_cfg& mc, hipStream_t s) {
   DDMI_REQUIRE((long)a.K * a.C <= (1L << 30), DDMI_ERR_CAPACITY, "ddmi_pose_metrics: n_refs * ceil(n_perms / 64) exceeds 2^30");
   const size_t pk = (size_t)a.P * a.K, key_bytes = round_up((long)(pk * a.C * sizeof(unsigned long long)), 256);
   const size_t bytes = key_bytes + 2 * pk * sizeof(float);
-  if (bytes > m.metrics_ws_bytes) {
-    m.mpool.release();
-    m.metrics_ws = nullptr; m.metrics_ws_bytes = 0;
-    m.metrics_ws = m.mpool.alloc_bytes(bytes);
-    m.metrics_ws_bytes = bytes;
-  }
+  metrics_scratch(m, bytes);
   a.part_key = reinterpret_cast<unsigned long long*>(m.metrics_ws);
   a.part_plain = reinterpret_cast<float*>(reinterpret_cast<char*>(m.metrics_ws) + key_bytes);
   a.part_cd = a.part_plain + pk;
   a.rmsd = mc.rmsd; a.best = mc.best; a.rmsd_per_ref = mc.rmsd_per_ref; a.rmsd_plain = mc.rmsd_plain;
   a.centroid = mc.centroid_distance; a.min_self = mc.min_self_distance; a.min_point = mc.min_point_distance;
   launch_pose_metrics(a, s);
+}
+
+// ddmi_pose_fit shares the scratch of ddmi_pose_metrics (one 64-bit word per (pose, reference, chunk)): calls on one stream are ordered.
+void pose_fit(Model& m, const ddmi_pose_fit_cfg& fc, hipStream_t s) {
+  PoseFitArgs a{};
+  a.pos = fc.pos; a.ref = fc.ref; a.perm = fc.perm; a.atom_index = fc.atom_index;
+  a.P = fc.n_poses; a.n = fc.n_atoms; a.m = fc.n_kept; a.K = fc.n_refs; a.S = fc.perm ? fc.n_perms : 1;
+  a.C = cdiv(a.S, MET_CHUNK);
+  DDMI_REQUIRE((long)a.K * a.C <= (1L << 30), DDMI_ERR_CAPACITY, "ddmi_pose_fit: n_refs * ceil(n_perms / 64) exceeds 2^30");
+  metrics_scratch(m, (size_t)a.P * a.K * a.C * sizeof(unsigned long long));
+  a.part_key = reinterpret_cast<unsigned long long*>(m.metrics_ws);
+  a.rmsd_min = fc.rmsd_min; a.best_min = fc.best_min; a.rmsd_min_per_ref = fc.rmsd_min_per_ref;
+  a.rotation = fc.rotation; a.translation = fc.translation;
+  launch_pose_fit(a, s);
 }
 
 void sample(Model& m, float* lig_pos, const ddmi_sample_cfg& sc, hipStream_t s) {

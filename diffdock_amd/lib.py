@@ -152,6 +152,13 @@ class PoseMetricsCfg(C.Structure):   # ddmi_pose_metrics_cfg (include/ddmi.h)
                                           "centroid_distance", "min_self_distance", "min_point_distance")]
 
 
+class PoseFitCfg(C.Structure):   # ddmi_pose_fit_cfg (include/ddmi.h)
+    _fields_ = [("struct_size", C.c_uint32)] + \
+               [(n, C.c_int32) for n in ("n_poses", "n_atoms", "n_kept", "n_refs", "n_perms")] + \
+               [(n, C.c_void_p) for n in ("pos", "ref", "perm", "atom_index", "rmsd_min", "best_min", "rmsd_min_per_ref", "rotation",
+                                          "translation")]
+
+
 def make_config(cfg) -> Config:
     c = Config()
     for name, _ in Config._fields_:
@@ -198,6 +205,7 @@ _DECLS = {
     "ddmi_set_sample_record": (C.c_int, [C.c_void_p, C.POINTER(SampleRecord)]),
     "ddmi_randomize_position": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RandomizeCfg), C.c_void_p]),
     "ddmi_pose_metrics": (C.c_int, [C.c_void_p, C.POINTER(PoseMetricsCfg), C.c_void_p]),
+    "ddmi_pose_fit": (C.c_int, [C.c_void_p, C.POINTER(PoseFitCfg), C.c_void_p]),
     "ddmi_perturb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SampleCfg), C.c_int, C.c_void_p]),
     "ddmi_debug_shape": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ddmi_debug_read": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -72,18 +72,23 @@ def confidence_order(confidence):
     return torch.argsort(c, stable=True).flip(0)
 
 
-def evaluate_poses(pos, ref, *, model, perm=None, atom_index=None, points=None, confidence=None, per_ref=False):
+def evaluate_poses(pos, ref, *, model, perm=None, atom_index=None, points=None, confidence=None, per_ref=False, minimize=False):
     """`model.pose_metrics` (any MIScoreModel: it lends its device and stream) plus what follows from the values, all on the device:
     rmsd_below_2 / rmsd_below_5 flags per pose, `complete` (False when `perm` is an Isomorphisms cut short: the RMSDs are then upper
     bounds), and with `confidence` [N] or [N, outputs]: `order` (evaluate.py:488-493), `top1_rmsd` = the RMSD of the most confident
     pose, `top5_rmsd` = the smallest among the five most confident (evaluate.py:627).  For a trajectory [T, N, n, 3] the ordering of
-    the N poses applies to every step: top1_rmsd / top5_rmsd are [T]."""
+    the N poses applies to every step: top1_rmsd / top5_rmsd are [T].
+    `minimize=True` adds the outputs of `model.pose_fit` (ddmi_pose_fit: rmsd_min = spyrmsd's symmrmsd with minimize=True, best_min,
+    rotation, translation, and rmsd_min_per_ref with per_ref) and, with `confidence`, top1_rmsd_min / top5_rmsd_min built as
+    top1_rmsd / top5_rmsd are.  Without it nothing of that is computed."""
     complete = True
     if isinstance(perm, Isomorphisms):
         perm, complete = perm.perm, perm.complete
     out = model.pose_metrics(pos, ref, perm=perm, atom_index=atom_index, points=points, per_ref=per_ref)
     out["complete"] = complete
     out["rmsd_below_2"], out["rmsd_below_5"] = out["rmsd"] < 2.0, out["rmsd"] < 5.0
+    if minimize:
+        out.update(model.pose_fit(pos, ref, perm=perm, atom_index=atom_index, per_ref=per_ref))
     if confidence is not None:
         order = confidence_order(torch.as_tensor(confidence).to(out["rmsd"].device))
         if order.shape[0] != out["rmsd"].shape[-1]:
@@ -92,4 +97,17 @@ def evaluate_poses(pos, ref, *, model, perm=None, atom_index=None, points=None, 
         out["order"] = order
         out["top1_rmsd"] = ranked[..., 0]
         out["top5_rmsd"] = ranked[..., :5].min(dim=-1).values
+        if minimize:
+            ranked = out["rmsd_min"].index_select(-1, order)
+            out["top1_rmsd_min"] = ranked[..., 0]
+            out["top5_rmsd_min"] = ranked[..., :5].min(dim=-1).values
     return out
+
+
+def superpose(pos, fit):
+    """The poses moved onto their best known pose: `pos @ rotation^T + translation` with the transform `pose_fit` (or
+    `evaluate_poses(minimize=True)`) returned, on the device of `fit`, e.g. for writing aligned poses out.  The transform was fitted
+    on the kept atoms and is applied to all of `pos` [.., n, 3]."""
+    R, t = fit["rotation"], fit["translation"]
+    pos = torch.as_tensor(pos).to(R.device, R.dtype)
+    return pos @ R.transpose(-1, -2) + t.unsqueeze(-2)

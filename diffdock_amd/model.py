@@ -384,14 +384,8 @@ class MIScoreModel:
                 t.record_stream(torch.cuda.current_stream(dev))
         return pos
 
-    def pose_metrics(self, pos, ref, perm=None, atom_index=None, points=None, per_ref=False):
-        """Judge poses on the device (ddmi_pose_metrics; evaluate.py:474-505): `pos` [P, n, 3] or a trajectory [T, P, n, 3], `ref`
-        [K, m, 3] (or [m, 3]) known poses, `perm` int [S, m] graph isomorphisms as metrics.isomorphisms returns them (None = the
-        identity), `atom_index` int [m] the atoms of a pose that are compared, in the order of `ref` (None = all n; the reference's
-        filterHs), `points` [Q, 3] anything to keep clear of.  Returns a dict of device tensors with the leading shape of `pos`:
-        rmsd (symmetry-corrected, min over references), best [.., 2] int32 (the reference and the row of perm attaining it; ties go
-        to the lowest), rmsd_plain (identity only), centroid_distance, min_self_distance (+inf for one atom), min_point_distance
-        (+inf without points), and with per_ref rmsd_per_ref [.., K].  The call needs no complex and does not synchronise."""
+    def _pose_inputs(self, pos, ref, perm, atom_index):
+        """The shared inputs of pose_metrics / pose_fit on the device, checked: pos, ref [K, m, 3], perm, atom_index, lead, n, m."""
         dev = self.device
         pos = torch.as_tensor(pos).to(dev, torch.float32).contiguous()
         if pos.dim() not in (3, 4) or pos.shape[-1] != 3:
@@ -406,6 +400,46 @@ class MIScoreModel:
             raise ValueError(f"ref: [K, {m}, 3] expected, got {tuple(ref.shape)}")
         if perm is not None and (perm.dim() != 2 or perm.shape[1] != m):
             raise ValueError(f"perm: [S, {m}] expected, got {tuple(perm.shape)}")
+        return pos, ref, perm, atom_index, lead, n, m
+
+    def pose_fit(self, pos, ref, perm=None, atom_index=None, per_ref=False):
+        """The minimised symmetric RMSD and the fitting transform (ddmi_pose_fit; spyrmsd.rmsd.symmrmsd with minimize=True): inputs
+        as for `pose_metrics`.  Returns a dict of device tensors with the leading shape of `pos`: rmsd_min (the RMSD after the best
+        rigid superposition, min over references and rows of perm; exactly 0 where the reference's atol rule gives 0), best_min
+        [.., 2] int32 (the reference and the row attaining it; ties go to the lowest), rotation [.., 3, 3] and translation [.., 3]
+        of that superposition (`metrics.superpose` applies them), and with per_ref rmsd_min_per_ref [.., K].  The call needs no
+        complex and does not synchronise."""
+        dev = self.device
+        pos, ref, perm, atom_index, lead, n, m = self._pose_inputs(pos, ref, perm, atom_index)
+        P, K = int(np.prod(lead)), ref.shape[0]
+        f = lambda *shape, dtype=torch.float32: torch.empty(lead + shape, dtype=dtype, device=dev)
+        out = dict(rmsd_min=f(), best_min=f(2, dtype=torch.int32), rotation=f(3, 3), translation=f(3))
+        if per_ref:
+            out["rmsd_min_per_ref"] = f(K)
+        fc = _lib.PoseFitCfg()
+        fc.struct_size = C.sizeof(_lib.PoseFitCfg)
+        fc.n_poses, fc.n_atoms, fc.n_kept, fc.n_refs = P, n, m, K
+        fc.n_perms = 0 if perm is None else perm.shape[0]
+        inputs = dict(pos=pos, ref=ref, perm=perm, atom_index=atom_index)
+        for name, t in list(inputs.items()) + list(out.items()):
+            setattr(fc, name, None if t is None else t.data_ptr())
+        _lib.check(self.lib, self.lib.ddmi_pose_fit(self._h, C.byref(fc), self._stream()))
+        if dev.type == "cuda":   # converted copies of the inputs must outlive the enqueued kernels
+            for t in inputs.values():
+                if t is not None:
+                    t.record_stream(torch.cuda.current_stream(dev))
+        return out
+
+    def pose_metrics(self, pos, ref, perm=None, atom_index=None, points=None, per_ref=False):
+        """Judge poses on the device (ddmi_pose_metrics; evaluate.py:474-505): `pos` [P, n, 3] or a trajectory [T, P, n, 3], `ref`
+        [K, m, 3] (or [m, 3]) known poses, `perm` int [S, m] graph isomorphisms as metrics.isomorphisms returns them (None = the
+        identity), `atom_index` int [m] the atoms of a pose that are compared, in the order of `ref` (None = all n; the reference's
+        filterHs), `points` [Q, 3] anything to keep clear of.  Returns a dict of device tensors with the leading shape of `pos`:
+        rmsd (symmetry-corrected, min over references), best [.., 2] int32 (the reference and the row of perm attaining it; ties go
+        to the lowest), rmsd_plain (identity only), centroid_distance, min_self_distance (+inf for one atom), min_point_distance
+        (+inf without points), and with per_ref rmsd_per_ref [.., K].  The call needs no complex and does not synchronise."""
+        dev = self.device
+        pos, ref, perm, atom_index, lead, n, m = self._pose_inputs(pos, ref, perm, atom_index)
         if points is not None:
             points = torch.as_tensor(points).to(dev, torch.float32).reshape(-1, 3).contiguous()
             points = points if points.numel() else None

@@ -395,6 +395,40 @@ typedef struct ddmi_pose_metrics_cfg {
 } ddmi_pose_metrics_cfg;
 int ddmi_pose_metrics(ddmi_model* m, const ddmi_pose_metrics_cfg* cfg, ddmi_stream stream);
 
+/* The minimised symmetric RMSD and the fitting transform -- spyrmsd.rmsd.symmrmsd(..., minimize=True) (spyrmsd/rmsd.py:179-203 with
+ * spyrmsd/qcp.py): for every graph isomorphism the RMSD after the optimal rigid superposition (Theobald's QCP), then the min.  It
+ * separates "wrong conformer" from "right conformer in the wrong place".  Inputs, m-space, clamping and NULL rules are those of
+ * ddmi_pose_metrics_cfg.  For pose p, known pose k and row s of perm, with a_j = pos[p, atom_index[j]], b_j = ref[k, perm[s, j]]:
+ *   ca = mean_j a_j, cb = mean_j b_j, Ga = sum_j |a_j - ca|^2, Gb = sum_j |b_j - cb|^2, M = sum_j (a_j - ca)(b_j - cb)^T,
+ *   lambda = the largest eigenvalue of the symmetric 4x4 key matrix of M (qcp.py:55-122), e = Ga + Gb - 2 lambda,
+ *   rmsd_min = 0 where |e| < 1e-9 (the reference's atol, qcp.py:283), else sqrt(max(e, 0) / m),
+ * all in float64 on the float32 inputs (e is a small difference of large numbers); lambda comes from a cyclic Jacobi iteration, not
+ * from QCP's Newton iteration, so a degenerate largest eigenvalue needs no fallback.  The min over (k, s) is taken on e rounded to
+ * float32, which is the rounding of the float64 min.  Two kernels are enqueued and the call returns; no atomics, no host
+ * synchronisation, and every value is bit-identical whatever the other poses, known poses and permutations of the call are.
+ * rotation / translation: the proper rotation R (det = +1, QCP never reflects) and t = cb - R ca of the winning (k, s), so that
+ * R a_j + t ~ b_j.  m = 1 gives the identity.  Where the largest eigenvalue is degenerate (m = 2, collinear atoms) the optimal
+ * rotation is not unique: any maximiser is correct, one of them is returned.
+ * The errors are those of ddmi_pose_metrics (without the points rule), named ddmi_pose_fit_cfg. */
+typedef struct ddmi_pose_fit_cfg {
+  uint32_t struct_size;        /* sizeof of this struct the caller was built against                                        */
+  int32_t n_poses;             /* P: poses (steps * N for a trajectory)                                                     */
+  int32_t n_atoms;             /* n: atoms of a pose                                                                        */
+  int32_t n_kept;              /* m: atoms compared; = n_atoms without atom_index                                           */
+  int32_t n_refs;              /* K: known poses                                                                            */
+  int32_t n_perms;             /* S: rows of perm; ignored without perm                                                     */
+  const float* pos;            /* [P, n, 3]                                                                                 */
+  const float* ref;            /* [K, m, 3]                                                                                 */
+  const int32_t* perm;         /* [S, m] or NULL (identity, S = 1)                                                          */
+  const int32_t* atom_index;   /* [m] or NULL (0..n-1)                                                                      */
+  float* rmsd_min;             /* [P]  min over (k, s) of the minimised RMSD: symmrmsd(minimize=True), np.min over k        */
+  int32_t* best_min;           /* [P, 2]  the (k, s) attaining it; ties go to the lowest k * S + s                          */
+  float* rmsd_min_per_ref;     /* [P, K]  the value before the min over k                                                   */
+  float* rotation;             /* [P, 3, 3] row-major R of the winning (k, s)                                               */
+  float* translation;          /* [P, 3]  t = cb - R ca                                                                     */
+} ddmi_pose_fit_cfg;
+int ddmi_pose_fit(ddmi_model* m, const ddmi_pose_fit_cfg* cfg, ddmi_stream stream);
+
 /* Introspection for tests and profiling: copy a named internal buffer to the host.
  * ddmi_debug_shape returns the element count and up to 4 dims; names are listed in DESIGN.md. */
 int ddmi_debug_shape(ddmi_model* m, const char* name, int64_t shape[4], int* ndim, int* is_int);

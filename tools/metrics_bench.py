@@ -3,13 +3,16 @@
 (evaluate.py:474-505: copy the poses back, then spyrmsd's Python loop over all graph isomorphisms for every pose and reference) on
 the 576-isomorphism molecule of tests/golden/pose_metrics.pt.
 
-    python tools/metrics_bench.py [--molecule sym576|1a0q] [--reps R] [--warmup W]
+    python tools/metrics_bench.py [--molecule sym576|1a0q] [--reps R] [--warmup W] [--minimize]
 
   device  evaluate_poses(pos, ref, perm, confidence): every output of ddmi_pose_metrics plus the ordering, results left on the device;
           the clock stops after a device synchronisation
   host    pos.cpu(), then the loop of spyrmsd/rmsd.py:183-203 (one numpy gather, difference and sum per (pose, reference,
           isomorphism)) and the numpy one-liners of evaluate.py:486 and :503-505 -- spyrmsd.rmsd.symmrmsd itself when the package
           can be imported, else the restatement below, which the fixture generator checked to be equal to it to the last bit
+
+  --minimize  adds "pose_fit_ms": MIScoreModel.pose_fit (ddmi_pose_fit: the minimised RMSD over the same triples and the fitting
+          transform) alone, timed the same way; its host route (a scipy Newton iteration per triple) is not timed
 
 One JSON line: {"molecule", "poses", "refs", "isomorphisms", "device_ms", "host_ms", "speedup", "host_arm"} (medians).  Information
 only: nothing in the suite depends on these numbers."""
@@ -46,6 +49,7 @@ def main():
     ap.add_argument("--molecule", default="sym576")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--minimize", action="store_true")
     args = ap.parse_args()
     mol = torch.load(os.path.join(ROOT, "tests", "golden", "pose_metrics.pt"), weights_only=False)[args.molecule]
     m = MIScoreModel(TINY, device="cuda:0")          # pose metrics need a handle only: no weights, tables or complex
@@ -84,7 +88,16 @@ def main():
         return statistics.median(ts), out
     (d_ms, d_out), (h_ms, h_out) = timed(device), timed(host)
     assert np.abs(d_out.cpu().numpy() / h_out - 1).max() < 1e-5
-    print(json.dumps({"molecule": args.molecule, "poses": int(pos.shape[0]), "refs": int(ref.shape[0]), "isomorphisms": int(perm.shape[0]),
+    extra = {}
+    if args.minimize:
+        def fit():
+            out = m.pose_fit(pos, ref, perm=perm)
+            torch.cuda.synchronize()
+            return out["rmsd_min"]
+        f_ms, f_out = timed(fit)
+        assert bool((f_out <= d_out).all())
+        extra["pose_fit_ms"] = round(f_ms, 3)
+    print(json.dumps({**extra, "molecule": args.molecule, "poses": int(pos.shape[0]), "refs": int(ref.shape[0]), "isomorphisms": int(perm.shape[0]),
                       "device_ms": round(d_ms, 3), "host_ms": round(h_ms, 2), "speedup": round(h_ms / d_ms, 1), "host_arm": arm}))
 
 
