@@ -90,6 +90,8 @@ void ddmi_destroy(ddmi_model* h) {
   if (m.side_stream) { (void)hipStreamSynchronize(m.side_stream); (void)hipStreamDestroy(m.side_stream); }
   for (hipEvent_t e : {m.ev_fork, m.ev_join, m.ev_cross, m.ev_terms}) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : m.ev_pipe) (void)hipEventDestroy(e);
+  if (m.nbr_ev) { (void)hipEventSynchronize(m.nbr_ev); (void)hipEventDestroy(m.nbr_ev); }
+  if (m.nbr_host) (void)hipHostFree(m.nbr_host);
   delete h;
 }
 
@@ -255,6 +257,17 @@ int ddmi_pose_fit(ddmi_model* h, const ddmi_pose_fit_cfg* cfg, ddmi_stream s) {
     DDMI_REQUIRE(!cfg->perm || cfg->n_perms >= 1, DDMI_ERR_ARG, "ddmi_pose_fit_cfg: perm given with n_perms < 1");
     DDMI_CHECK_HIP(hipSetDevice(h->m.device));
     pose_fit(h->m, *cfg, (hipStream_t)s);
+  });
+}
+
+int ddmi_neighbor_graph(ddmi_model* h, const ddmi_neighbor_graph_cfg* cfg, ddmi_stream s) {
+  return guard([&] {
+    DDMI_REQUIRE(h && cfg, DDMI_ERR_ARG, "null argument");
+    DDMI_REQUIRE(cfg->struct_size == sizeof(ddmi_neighbor_graph_cfg), DDMI_ERR_ARG, "ddmi_neighbor_graph_cfg.struct_size does not match this library");
+    DDMI_REQUIRE(cfg->pos && cfg->ptr, DDMI_ERR_ARG, "ddmi_neighbor_graph_cfg: pos and ptr are required");
+    DDMI_REQUIRE(cfg->n_nodes > 0 && cfg->n_sets > 0, DDMI_ERR_ARG, "ddmi_neighbor_graph_cfg: n_nodes and n_sets must be positive");
+    DDMI_CHECK_HIP(hipSetDevice(h->m.device));
+    neighbor_graph(h->m, *cfg, (hipStream_t)s);
   });
 }
 

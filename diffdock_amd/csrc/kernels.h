@@ -417,4 +417,18 @@ struct PoseFitArgs {
 };
 void launch_pose_fit(const PoseFitArgs& a, hipStream_t s);
 
+// ddmi_neighbor_graph (k_neighbors.hip): capped neighbour lists of a ragged batch of point sets.  ptr [G + 1], c2 [G] (cutoff squared,
+// float32 product) and cap [G] are device arrays; cnt [N] is scratch (the in-cutoff count of every node, before the cap).
+// launch_neighbor_count fills cnt and deg; after the exclusive scan of deg into offsets, launch_neighbor_fill writes the columns
+// [offsets[i], offsets[i + 1]) of edge [2][capacity] (row 0 neighbour, row 1 centre, global row numbers; columns >= capacity are dropped).
+// A node with more in-cutoff candidates than NBR_STAGE per-wave LDS slots is selected by repeated minimum scans instead.
+constexpr int NBR_WAVES = 4, NBR_STAGE = 1024;
+struct NeighborArgs {
+  const float* pos; const int* ptr; const float* c2; const int* cap; int N, G;
+  int *cnt, *deg; const int* offsets;
+  long long* edge; long long capacity;
+};
+void launch_neighbor_count(const NeighborArgs& a, hipStream_t s);
+void launch_neighbor_fill(const NeighborArgs& a, hipStream_t s);
+
 }  // namespace ddmi

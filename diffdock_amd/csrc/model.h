@@ -139,6 +139,8 @@ struct Model {
   double crop_cutoff = 0.0;  // > 0: receptor cropped to this distance from the ligand in ddmi_forward (crop_beyond)
   DevicePool cpool;
   DevicePool mpool; void* metrics_ws = nullptr; size_t metrics_ws_bytes = 0;   // ddmi_pose_metrics / ddmi_pose_fit scratch: grows, never shrinks
+  DevicePool npool; void* nbr_ws = nullptr; size_t nbr_ws_bytes = 0;           // ddmi_neighbor_graph scratch: grows, never shrinks
+  int32_t* nbr_host = nullptr; size_t nbr_host_words = 0; hipEvent_t nbr_ev = nullptr;   // pinned staging of its per-set table
   struct Cx;  // cx.h
   std::shared_ptr<Cx> cx;
   std::map<std::string, DebugEntry> debug;
@@ -184,5 +186,7 @@ void randomize_position(Model& m, float* lig_pos, const ddmi_randomize_cfg& rc, 
 // RMSDs and clearances of poses against reference poses (evaluate.py:474-505); needs no complex
 void pose_metrics(Model& m, const ddmi_pose_metrics_cfg& mc, hipStream_t s);
 void pose_fit(Model& m, const ddmi_pose_fit_cfg& fc, hipStream_t s);
+// capped neighbour lists of a ragged batch of point sets (process_mols.py:171-192, :207-228); needs no complex
+void neighbor_graph(Model& m, const ddmi_neighbor_graph_cfg& nc, hipStream_t s);
 
 }  // namespace ddmi

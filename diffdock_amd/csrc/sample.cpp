@@ -198,6 +198,68 @@ void pose_fit(Model& m, const ddmi_pose_fit_cfg& fc, hipStream_t s) {
   launch_pose_fit(a, s);
 }
 
+// ddmi_neighbor_graph: the per-set table (ptr, cutoff squared, cap) is checked on the host and rides through a pinned staging buffer as
+// the centres of randomize_position do -- consumed before this returns, nothing waits for the stream; then count -> scan -> fill.
+void neighbor_graph(Model& m, const ddmi_neighbor_graph_cfg& nc, hipStream_t s) {
+  const int N = nc.n_nodes, G = nc.n_sets;
+  DDMI_REQUIRE(nc.ptr[0] == 0 && nc.ptr[G] == N, DDMI_ERR_ARG, "ddmi_neighbor_graph_cfg.ptr must run from 0 to n_nodes");
+  const size_t words = 3 * (size_t)G + 1;
+  if (words > m.nbr_host_words) {
+    if (m.nbr_ev) DDMI_CHECK_HIP(hipEventSynchronize(m.nbr_ev));
+    else DDMI_CHECK_HIP(hipEventCreate(&m.nbr_ev));
+    if (m.nbr_host) { (void)hipHostFree(m.nbr_host); m.nbr_host = nullptr; m.nbr_host_words = 0; }
+    DDMI_CHECK_HIP(hipHostMalloc(reinterpret_cast<void**>(&m.nbr_host), words * sizeof(int32_t)));
+    m.nbr_host_words = words;
+  } else {
+    DDMI_CHECK_HIP(hipEventSynchronize(m.nbr_ev));
+  }
+  int32_t* h_ptr = m.nbr_host;
+  float* h_c2 = reinterpret_cast<float*>(m.nbr_host + G + 1);
+  int32_t* h_cap = m.nbr_host + 2 * (size_t)G + 1;
+  long long bound = 0;
+  bool capped = true;
+  for (int g = 0; g < G; ++g) {
+    const long long n = (long long)nc.ptr[g + 1] - nc.ptr[g];
+    DDMI_REQUIRE(n >= 0, DDMI_ERR_ARG, "ddmi_neighbor_graph_cfg.ptr decreases");
+    const float c = nc.set_cutoff ? nc.set_cutoff[g] : nc.cutoff;
+    DDMI_REQUIRE(c > 0.f, DDMI_ERR_ARG, "ddmi_neighbor_graph_cfg: a cutoff must be positive");   // (false for NaN)
+    const int cap = nc.set_max_neighbors ? nc.set_max_neighbors[g] : nc.max_neighbors;
+    DDMI_REQUIRE(cap >= 0, DDMI_ERR_ARG, "ddmi_neighbor_graph_cfg: max_neighbors must not be negative");
+    capped = capped && cap > 0;
+    h_ptr[g] = nc.ptr[g]; h_c2[g] = c * c; h_cap[g] = cap > 0 ? cap : 1000;
+    bound += n * std::min<long long>(h_cap[g], std::max<long long>(n - 1, 0));
+  }
+  h_ptr[G] = N;
+  DDMI_REQUIRE(bound < (1LL << 31), DDMI_ERR_CAPACITY, "ddmi_neighbor_graph: the edge bound of the call reaches 2^31");
+  DDMI_REQUIRE(nc.capacity >= 0 && (!nc.edge_index || !capped || nc.capacity >= bound), DDMI_ERR_ARG,
+               "ddmi_neighbor_graph_cfg.capacity is below sum n_g * min(max_neighbors, n_g - 1), the edge bound of a capped call");
+  const size_t tab_bytes = round_up((long)(words * sizeof(int32_t)), 256), row_bytes = round_up((long)(((size_t)N + 1) * sizeof(int)), 256);
+  const size_t bytes = tab_bytes + 3 * row_bytes;
+  if (bytes > m.nbr_ws_bytes) {   // (hipFree waits for the device: kernels of an earlier call keep their memory)
+    m.npool.release();
+    m.nbr_ws = nullptr; m.nbr_ws_bytes = 0;
+    m.nbr_ws = m.npool.alloc_bytes(bytes);
+    m.nbr_ws_bytes = bytes;
+  }
+  char* ws = reinterpret_cast<char*>(m.nbr_ws);
+  DDMI_CHECK_HIP(hipMemcpyAsync(ws, m.nbr_host, words * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  DDMI_CHECK_HIP(hipEventRecord(m.nbr_ev, s));
+  NeighborArgs a{};
+  a.pos = nc.pos; a.N = N; a.G = G;
+  a.ptr = reinterpret_cast<const int*>(ws);
+  a.c2 = reinterpret_cast<const float*>(ws) + G + 1;
+  a.cap = reinterpret_cast<const int*>(ws) + 2 * (size_t)G + 1;
+  a.cnt = reinterpret_cast<int*>(ws + tab_bytes);
+  a.deg = nc.deg ? nc.deg : reinterpret_cast<int*>(ws + tab_bytes + row_bytes);
+  int* offsets = nc.offsets ? nc.offsets : reinterpret_cast<int*>(ws + tab_bytes + 2 * row_bytes);
+  a.offsets = offsets;
+  a.edge = reinterpret_cast<long long*>(nc.edge_index); a.capacity = nc.capacity;
+  launch_neighbor_count(a, s);
+  launch_exclusive_scan(a.deg, offsets, N, s);
+  if (nc.n_edges) DDMI_CHECK_HIP(hipMemcpyAsync(nc.n_edges, offsets + N, sizeof(int), hipMemcpyDeviceToDevice, s));
+  if (nc.edge_index) launch_neighbor_fill(a, s);
+}
+
 void sample(Model& m, float* lig_pos, const ddmi_sample_cfg& sc, hipStream_t s) {
   DDMI_REQUIRE(m.has_complex, DDMI_ERR_STATE, "ddmi_set_complex must precede ddmi_sample");
   check_sample_cfg(m, sc);

@@ -48,9 +48,10 @@ BOND_TYPES = {1: 0, 2: 1, 3: 2, 4: 3}     # SDF bond order -> index in {SINGLE, 
 _HET_RESIDUES = {"MSE", "SEP", "TPO", "PTR", "CSO", "HYP", "MLY", "KCX", "CME", "CSD", "SEC", "PYL"}
 
 
-def _pdb_residues(path, extra_het_residues=()):
+def _pdb_residues(path, extra_het_residues=(), atoms=("N", "CA", "C")):
     """Residues with a CA atom, in file order: {name, chain, N, CA, C}; alternate locations other than ' ' / 'A' are
-    skipped; HETATM records count only for the modified amino acids ProDy's `protein` selection keeps (MSE, SEP, ...)."""
+    skipped; HETATM records count only for the modified amino acids ProDy's `protein` selection keeps (MSE, SEP, ...).
+    `atoms=None` keeps the first coordinate of EVERY atom name of the same residues."""
     res, order = {}, []
     with open(path) as f:
         for line in f:
@@ -58,7 +59,7 @@ def _pdb_residues(path, extra_het_residues=()):
             if not (line.startswith("ATOM") or (het and (line[17:20].strip() in _HET_RESIDUES or line[17:20].strip() in extra_het_residues))):
                 continue
             atom = line[12:16].strip()
-            if atom not in ("N", "CA", "C") or line[16] not in (" ", "A"):
+            if (atoms is not None and atom not in atoms) or line[16] not in (" ", "A"):
                 continue
             key = (line[21], line[22:27])
             if key not in res:
@@ -103,6 +104,119 @@ def receptor_graph(coords, neighbor_cutoff=15.0, max_neighbors=24):
         src_list += [i] * len(dst)
         dst_list += [int(x) for x in dst]
     return np.asarray([dst_list, src_list], dtype=np.int64)
+
+
+# ---------------------------------------------------------------------------------------------- all-atom receptor
+# Heavy atoms per residue in the order the reference's [n_res, 14, 3] table uses (datasets/constants.py atom_order): backbone
+# N CA C O, then the side chain.  Tryptophan's ring is listed CD1 CD2 CE2 CE3 NE1 CZ2 CZ3 CH2 there, not in the wwPDB order
+# (CD1 CD2 NE1 CE2 CE3 ...): row positions are part of the format, so that order is kept.
+_BACKBONE = "N CA C O"
+_SIDE_CHAIN = {"G": "", "A": "CB", "S": "CB OG", "C": "CB SG", "T": "CB OG1 CG2", "P": "CB CG CD", "V": "CB CG1 CG2",
+               "M": "CB CG SD CE", "N": "CB CG OD1 ND2", "I": "CB CG1 CG2 CD1", "L": "CB CG CD1 CD2", "D": "CB CG OD1 OD2",
+               "E": "CB CG CD OE1 OE2", "K": "CB CG CD CE NZ", "Q": "CB CG CD OE1 NE2", "H": "CB CG ND1 CD2 CE1 NE2",
+               "F": "CB CG CD1 CD2 CE1 CE2 CZ", "R": "CB CG CD NE CZ NH1 NH2", "Y": "CB CG CD1 CD2 CE1 CE2 CZ OH",
+               "W": "CB CG CD1 CD2 CE2 CE3 NE1 CZ2 CZ3 CH2", "X": ""}
+ATOM_ORDER = {k: (_BACKBONE + " " + v).split() for k, v in _SIDE_CHAIN.items()}
+_ONE_LETTER = dict(zip(POSSIBLE_AMINO_ACIDS[:20], "ARNDCQEGHILKMFPSTWYV"))
+_ONE_LETTER["MSE"] = "M"     # selenomethionine reads as methionine (its SE atom is not `SD`: that row stays absent)
+_LONG_NAME = {v: k for k, v in _ONE_LETTER.items() if k != "MSE"}
+ATOM_TYPE_2 = ['C*', 'CA', 'CB', 'CD', 'CE', 'CG', 'CH', 'CZ', 'N*', 'ND', 'NE', 'NH', 'NZ', 'O*', 'OD', 'OE', 'OG', 'OH', 'OX', 'S*',
+               'SD', 'SG', 'misc']
+ATOM_TYPE_3 = ['C', 'CA', 'CB', 'CD', 'CD1', 'CD2', 'CE', 'CE1', 'CE2', 'CE3', 'CG', 'CG1', 'CG2', 'CH2', 'CZ', 'CZ2', 'CZ3', 'N',
+               'ND1', 'ND2', 'NE', 'NE1', 'NE2', 'NH1', 'NH2', 'NZ', 'O', 'OD1', 'OD2', 'OE1', 'OE2', 'OG', 'OG1', 'OH', 'OXT', 'SD',
+               'SG', 'misc']
+
+
+def _last_if_absent(vocabulary, item):
+    return vocabulary.index(item) if item in vocabulary else len(vocabulary) - 1
+
+
+def read_pdb_atoms(path, extra_het_residues=()):
+    """-> (coords float64 [n_res, 14, 3], residue names): the heavy atoms of every residue with a CA atom -- the residues of
+    `read_pdb_calpha`, same alternate-location and HETATM rules -- in the reference's per-residue order (`ATOM_ORDER`,
+    datasets/parse_chi.py:62-74 get_coords), NaN where the file has no such atom.  Per residue the FIRST coordinate of each atom
+    name counts.  The table is keyed by the residue NAME: the 20 standard names and MSE (as M); any other residue keeps its four
+    backbone atoms only."""
+    rs = _pdb_residues(path, extra_het_residues, atoms=None)
+    coords = np.full((len(rs), 14, 3), np.nan, dtype=np.float64)
+    for i, r in enumerate(rs):
+        for j, atom in enumerate(ATOM_ORDER[_ONE_LETTER.get(r["name"], "X")]):
+            if atom in r:
+                coords[i, j] = r[atom]
+    return coords, [r["name"] for r in rs]
+
+
+def receptor_atom_features(names, coords):
+    """get_moad_atom_feats (datasets/process_mols.py:244-276) for every residue -> (features int64 [n_atom, 4], atom_rec_contact
+    int64 [2, n_atom]).  The columns index the amino-acid, atomic-number, `atom_type_2` and `atom_type_3` vocabularies
+    (config.REC_ATOM_FEATURE_DIMS = (38, 119, 23, 38)); rows are the atoms of `coords` [n_res, 14, 3] that are not NaN, in residue
+    order; atom_rec_contact = [arange(n_atom); residue of the atom], the form the device crop requires.  The reference keys the
+    features by the one-letter sequence (ProDy's `pdb.ca.getSequence()`): a standard residue by its letter, MSE as M.
+    DIFFERENCE: a residue with no letter (X) gets 'misc' in all four columns on its backbone atoms; the reference raises KeyError
+    there (`aa_short2long['X']`) and its caller skips the whole complex."""
+    coords = np.asarray(coords, dtype=np.float64).reshape(-1, 14, 3)
+    feats, owner = [], []
+    for i, name in enumerate(names):
+        letter = _ONE_LETTER.get(name, "X")
+        order = ATOM_ORDER[letter]
+        for j in np.where(~np.isnan(coords[i]).any(axis=1))[0]:
+            if letter == "X" or j >= len(order):
+                row = [len(POSSIBLE_AMINO_ACIDS) - 1 if letter == "X" else POSSIBLE_AMINO_ACIDS.index(_LONG_NAME[letter]),
+                       118, len(ATOM_TYPE_2) - 1, len(ATOM_TYPE_3) - 1]
+            else:
+                atom = order[j]
+                row = [POSSIBLE_AMINO_ACIDS.index(_LONG_NAME[letter]), _Z[atom[:1]] - 1,      # (element = first letter of the name)
+                       _last_if_absent(ATOM_TYPE_2, (atom + "*")[:2]), _last_if_absent(ATOM_TYPE_3, atom)]
+            feats.append(row)
+            owner.append(i)
+    feats = np.asarray(feats, dtype=np.int64).reshape(-1, 4)
+    return feats, np.stack([np.arange(len(owner), dtype=np.int64), np.asarray(owner, dtype=np.int64)])
+
+
+def _per_set(value, n_sets, default=None):
+    if np.ndim(value) == 0:
+        return [default if value is None else value] * n_sets
+    if len(value) != n_sets:
+        raise ValueError(f"one value or one per set ({n_sets}) expected, got {len(value)}")
+    return [default if v is None else v for v in value]
+
+
+def neighbor_graph(coords, cutoff, max_neighbors, model=None, ptr=None):
+    """Neighbour lists of one point set, or of the independent sets `ptr` [G + 1] splits the rows into -> edge_index int64 numpy
+    [2, E] = [neighbour; centre], ordered by centre.  The rule is ddmi_neighbor_graph's (include/ddmi.h; the loop of
+    new_extract_receptor_structure, datasets/process_mols.py:171-192 / :207-228): the other nodes of the set closer than `cutoff`
+    (strict); all of them in ascending index if at most `max_neighbors` (None / 0 = 1000), else the nearest in ascending
+    (distance, index); the nearest other node if there is none.  The node itself is excluded by index, another node at distance 0 is
+    a neighbour, ties go to the lower index.  `cutoff` / `max_neighbors`: one value or one per set.
+    With `model` (an MIScoreModel) the lists are built on its device: float32 direct differences.  Without one this host
+    restatement runs: the same rule in float64 on the float32-rounded coordinates -- the oracle of the kernel's tests."""
+    if model is not None:
+        return model.neighbor_graph(coords, cutoff, max_neighbors, ptr=ptr)[0].cpu().numpy()
+    x = np.asarray(coords, dtype=np.float32).astype(np.float64).reshape(-1, 3)
+    ptr = np.asarray([0, len(x)] if ptr is None else ptr, dtype=np.int64)
+    G = len(ptr) - 1
+    cutoffs, caps = _per_set(cutoff, G), _per_set(max_neighbors, G, 0)
+    nbr, ctr = [], []
+    for g in range(G):
+        lo, hi = int(ptr[g]), int(ptr[g + 1])
+        c2, cap = float(cutoffs[g]) ** 2, int(caps[g]) or 1000
+        for b in range(lo, hi, 512):      # row blocks: no n x n matrix for a large set
+            rows = np.arange(b, min(b + 512, hi))
+            dx = x[rows, None, :] - x[None, lo:hi, :]
+            d2 = dx[..., 0] * dx[..., 0] + dx[..., 1] * dx[..., 1] + dx[..., 2] * dx[..., 2]
+            d2[np.arange(len(rows)), rows - lo] = np.inf      # the node itself, by index
+            for r, i in enumerate(rows):
+                inside = np.nonzero(d2[r] < c2)[0]
+                if len(inside) > cap:
+                    inside = inside[d2[r, inside] <= np.partition(d2[r, inside], cap - 1)[cap - 1]]      # (ties at the cap-th kept for the sort)
+                    inside = inside[np.argsort(d2[r, inside], kind="stable")[:cap]]      # stable: equal distances keep index order
+                elif len(inside) == 0 and hi - lo > 1:
+                    inside = np.asarray([np.argmin(d2[r])])                              # (the first minimum: the lower index)
+                nbr.append(inside + lo)
+                ctr.append(np.full(len(inside), i, dtype=np.int64))
+    if not nbr:
+        return np.zeros((2, 0), dtype=np.int64)
+    return np.stack([np.concatenate(nbr), np.concatenate(ctr)]).astype(np.int64)
 
 
 def read_sdf(path, remove_hs=True):
@@ -246,11 +360,17 @@ def transformation_mask(n_atoms, edge_index):
 
 
 def complex_graph(pdb_path, sdf_path, receptor_radius=15.0, c_alpha_max_neighbors=24, lm_embeddings=None, atom_features=None,
-                  lm_dim=1280, name=None) -> HeteroData:
+                  lm_dim=1280, name=None, all_atoms=False, atom_radius=5.0, atom_max_neighbors=8, model=None) -> HeteroData:
     """HeteroData with the schema of the reference's preprocessed complex: receptor C-alpha graph, ligand
     heavy-atom graph with rotatable-bond masks, both centred on the receptor's C-alpha centroid (`original_center`,
     datasets/pdbbind.py get_complex).  `lm_embeddings` [n_res, 1280] and `atom_features` [n_lig, 16] are the external
-    inputs (ESM, RDKit); zeros / the connection-table columns of `ligand_atom_features` when absent."""
+    inputs (ESM, RDKit); zeros / the connection-table columns of `ligand_atom_features` when absent.
+    `all_atoms=True` adds the receptor's heavy atoms (process_mols.py:203-239): g['atom'].x [n_atom, 4] (`receptor_atom_features`),
+    g['atom'].pos centred with the receptor (utils/inference_utils.py:231-234), `atom_contact` (neighbours within `atom_radius`,
+    at most `atom_max_neighbors`) and `atom_rec_contact`.  With `model=` (an MIScoreModel) BOTH neighbour graphs, residues and
+    atoms, come from one ddmi_neighbor_graph call on the model's device (float32 direct differences, `neighbor_graph`); without
+    it the residue graph is `receptor_graph` (the reference's torch.cdist arithmetic) and the atom graph the host restatement of
+    `neighbor_graph`."""
     rc, rtype, _ = read_pdb_calpha(pdb_path)
     lc, z, bonds = read_sdf(sdf_path)
     g = HeteroData()
@@ -262,10 +382,32 @@ def complex_graph(pdb_path, sdf_path, receptor_radius=15.0, c_alpha_max_neighbor
     lm = torch.zeros(len(rc), lm_dim) if lm_embeddings is None else torch.as_tensor(lm_embeddings, dtype=torch.float32)
     g["receptor"].x = torch.cat([torch.from_numpy(rtype.astype(np.float32))[:, None], lm], 1)
     g["receptor"].side_chain_vecs = torch.zeros(len(rc), 10)
-    g["receptor", "rec_contact", "receptor"].edge_index = torch.from_numpy(
-        receptor_graph(rpos.numpy(), receptor_radius, c_alpha_max_neighbors))
     center = torch.mean(rpos, dim=0, keepdim=True)
+    if all_atoms:
+        table, names = read_pdb_atoms(pdb_path)
+        assert len(table) == len(rc)
+        afeat, atom_rec = receptor_atom_features(names, table)
+        flat = table.reshape(-1, 3)
+        apos = torch.from_numpy(flat[~np.isnan(flat).any(axis=1)].astype(np.float32))
+    # both graphs are built on the uncentred float32 coordinates, like the reference's
+    if model is None:
+        rec_ei = receptor_graph(rpos.numpy(), receptor_radius, c_alpha_max_neighbors)
+        atom_ei = neighbor_graph(apos.numpy(), atom_radius, atom_max_neighbors) if all_atoms else None
+    elif all_atoms:     # one ragged call: set 0 the residues, set 1 the atoms
+        n_res = len(rpos)
+        both = neighbor_graph(torch.cat([rpos, apos]).numpy(), (receptor_radius, atom_radius), (c_alpha_max_neighbors, atom_max_neighbors),
+                              model=model, ptr=[0, n_res, n_res + len(apos)])
+        of_rec = both[1] < n_res
+        rec_ei, atom_ei = both[:, of_rec], both[:, ~of_rec] - n_res
+    else:
+        rec_ei = neighbor_graph(rpos.numpy(), receptor_radius, c_alpha_max_neighbors, model=model)
+    g["receptor", "rec_contact", "receptor"].edge_index = torch.from_numpy(np.ascontiguousarray(rec_ei))
     g["receptor"].pos = rpos - center
+    if all_atoms:
+        g["atom"].x = torch.from_numpy(afeat.astype(np.float32))
+        g["atom"].pos = apos - center
+        g["atom", "atom_contact", "atom"].edge_index = torch.from_numpy(np.ascontiguousarray(atom_ei))
+        g["atom", "atom_rec_contact", "receptor"].edge_index = torch.from_numpy(atom_rec)
     ei, attr = ligand_bond_arrays(bonds)
     if atom_features is None:       # the connection-table columns; the perception columns stay 0 (module docstring)
         feats = ligand_atom_features(sdf_path)

@@ -159,6 +159,12 @@ class PoseFitCfg(C.Structure):   # ddmi_pose_fit_cfg (include/ddmi.h)
                                           "translation")]
 
 
+class NeighborGraphCfg(C.Structure):   # ddmi_neighbor_graph_cfg (include/ddmi.h)
+    _fields_ = [("struct_size", C.c_uint32), ("n_nodes", C.c_int32), ("n_sets", C.c_int32), ("max_neighbors", C.c_int32),
+                ("cutoff", C.c_float), ("capacity", C.c_int64)] + \
+               [(n, C.c_void_p) for n in ("pos", "ptr", "set_cutoff", "set_max_neighbors", "deg", "offsets", "edge_index", "n_edges")]
+
+
 def make_config(cfg) -> Config:
     c = Config()
     for name, _ in Config._fields_:
@@ -206,6 +212,7 @@ _DECLS = {
     "ddmi_randomize_position": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RandomizeCfg), C.c_void_p]),
     "ddmi_pose_metrics": (C.c_int, [C.c_void_p, C.POINTER(PoseMetricsCfg), C.c_void_p]),
     "ddmi_pose_fit": (C.c_int, [C.c_void_p, C.POINTER(PoseFitCfg), C.c_void_p]),
+    "ddmi_neighbor_graph": (C.c_int, [C.c_void_p, C.POINTER(NeighborGraphCfg), C.c_void_p]),
     "ddmi_perturb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SampleCfg), C.c_int, C.c_void_p]),
     "ddmi_debug_shape": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ddmi_debug_read": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -464,6 +464,57 @@ class MIScoreModel:
                     t.record_stream(torch.cuda.current_stream(dev))
         return out
 
+    def neighbor_graph(self, pos, cutoff, max_neighbors=None, ptr=None):
+        """Capped neighbour lists on the device (ddmi_neighbor_graph; the loop of new_extract_receptor_structure,
+        datasets/process_mols.py:171-192 and :207-228): `pos` [N, 3]; `ptr` [G + 1] (host integers) splits the rows into G
+        independent point sets (None = one set); `cutoff` and `max_neighbors` are one value or one per set (None / 0 = the
+        reference's 1000).  Returns (edge_index [2, E] int64 = [neighbour; centre] ordered by centre, global row numbers, and deg [N]
+        int32) as device tensors.  The library call does not synchronise; this wrapper reads the edge total once to shape the result
+        (an uncapped set: once to size the buffer, before the columns are written).  The call needs no complex."""
+        dev = self.device
+        pos = torch.as_tensor(pos).to(dev, torch.float32).reshape(-1, 3).contiguous()
+        N = pos.shape[0]
+        ptr = np.ascontiguousarray([0, N] if ptr is None else np.asarray(ptr).reshape(-1), dtype=np.int32)
+        G = len(ptr) - 1
+        per_set = lambda v, dt: None if np.ndim(v) == 0 else np.ascontiguousarray(np.asarray([0 if x is None else x for x in v]), dtype=dt)
+        cut, cap = per_set(cutoff, np.float32), per_set(max_neighbors, np.int32)
+        for name, arr in (("cutoff", cut), ("max_neighbors", cap)):
+            if arr is not None and len(arr) != G:
+                raise ValueError(f"{name}: one value or one per set ({G}) expected, got {len(arr)}")
+        caps = np.full(max(G, 0), int(max_neighbors or 0), dtype=np.int64) if cap is None else cap.astype(np.int64)
+        n = np.diff(ptr.astype(np.int64)) if G >= 1 else np.zeros(0, dtype=np.int64)
+        bound = int(np.sum(np.maximum(n, 0) * np.minimum(np.where(caps > 0, caps, 1000), np.maximum(n - 1, 0))))
+        deg = torch.empty(N, dtype=torch.int32, device=dev)
+        n_edges = torch.zeros(1, dtype=torch.int32, device=dev)
+        nc = _lib.NeighborGraphCfg()
+        nc.struct_size = C.sizeof(_lib.NeighborGraphCfg)
+        nc.n_nodes, nc.n_sets = N, G
+        nc.max_neighbors = 0 if cap is not None else int(max_neighbors or 0)
+        nc.cutoff = 0.0 if cut is not None else float(cutoff)
+        nc.pos, nc.ptr = pos.data_ptr() if N else None, ptr.ctypes.data
+        nc.set_cutoff = None if cut is None else cut.ctypes.data
+        nc.set_max_neighbors = None if cap is None else cap.ctypes.data
+        nc.deg, nc.n_edges = deg.data_ptr() if N else None, n_edges.data_ptr()
+
+        def call(edge):
+            nc.capacity = 0 if edge is None else edge.shape[1]
+            nc.edge_index = None if edge is None or edge.numel() == 0 else edge.data_ptr()
+            _lib.check(self.lib, self.lib.ddmi_neighbor_graph(self._h, C.byref(nc), self._stream()))
+        if bool((caps > 0).all()) and 0 < bound < (1 << 31):     # E <= bound is known before the call: one call, nothing read before it
+            edge = torch.empty(2, bound, dtype=torch.int64, device=dev)
+            call(edge)
+            E = int(n_edges.item())
+            edge = edge[:, :E].contiguous()
+        else:
+            call(None)
+            E = int(n_edges.item())
+            edge = torch.empty(2, E, dtype=torch.int64, device=dev)
+            if E:
+                call(edge)
+        if dev.type == "cuda":
+            pos.record_stream(torch.cuda.current_stream(dev))
+        return edge, deg
+
     def _sample_cfg(self, inference_steps, schedules, noise, seed, sample_ids, ode, no_random, no_final_step_noise,
                     temp_sampling, temp_psi, temp_sigma_data, crop_beyond):
         """ddmi_sample_cfg + the host / device arrays it points into (returned so that they outlive the call)."""

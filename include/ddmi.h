@@ -429,6 +429,48 @@ typedef struct ddmi_pose_fit_cfg {
 } ddmi_pose_fit_cfg;
 int ddmi_pose_fit(ddmi_model* m, const ddmi_pose_fit_cfg* cfg, ddmi_stream stream);
 
+/* Capped neighbour lists of a ragged batch of point sets -- the loop of new_extract_receptor_structure
+ * (datasets/process_mols.py:171-192 residues, :207-228 atoms) without its dense torch.cdist matrix.  Set g owns the rows
+ * ptr[g] .. ptr[g + 1] of pos.  For node i of set g, with c = cutoff and cap = max_neighbors of that set (0 = 1000, the reference's
+ * default):
+ *   candidates      the other nodes j != i of the set with d(i, j) < c (strict);
+ *   <= cap of them  all are kept, in ascending j;
+ *   > cap of them   the cap nearest are kept, in ascending distance;
+ *   none            the single nearest other node; a set of one node gets no edge.
+ * Rules of this library (DESIGN.md "Neighbour graphs"): the node itself is excluded by INDEX (the reference drops the first of an
+ * argsort over noisy distances, which is sometimes a real neighbour); another node at distance 0 is an ordinary neighbour; ties in
+ * distance go to the lower index (the selection key is float bits of d^2 << 32 | j); d^2 = dx dx + dy dy + dz dz in float32 from direct
+ * differences of the float32 coordinates, every operation rounded on its own, compared with the float32 product c c.  One wave owns a
+ * node and no atomic decides an order, so the row of node i is bit-identical whatever the other sets, G and the grid are.
+ * Outputs (device, each optional): deg [N]; offsets [N + 1] (exclusive scan of deg); n_edges = offsets[N]; edge_index [2, capacity]
+ * int64 = [neighbour; centre] with GLOBAL row numbers, ordered by centre -- the reference's [dst_list, src_list] -- row 1 starting at
+ * element `capacity`.  Only the first n_edges columns are written.  edge_index = NULL counts only.
+ * The handle gives the device, the stream order and the error text; scratch belongs to the handle and only grows.  Three kernels are
+ * enqueued and the call returns: no host synchronisation (the HOST arrays ptr / set_cutoff / set_max_neighbors are consumed before it
+ * returns).  When every set is capped, E <= sum_g n_g min(cap_g, n_g - 1) is known in advance and `capacity` must cover it.  With an
+ * uncapped set (max_neighbors 0) any capacity is accepted: columns past it are dropped and n_edges still holds the full total, so the
+ * caller may count first (edge_index = NULL), read n_edges once and call again.
+ * DDMI_ERR_ARG: struct_size mismatch, NULL pos or ptr, n_nodes < 1, n_sets < 1, ptr[0] != 0, ptr[n_sets] != n_nodes or a decreasing
+ * ptr, a cutoff <= 0 or NaN, max_neighbors < 0, capacity < 0 or too small for a capped call.  DDMI_ERR_CAPACITY: the edge bound of
+ * the call reaches 2^31. */
+typedef struct ddmi_neighbor_graph_cfg {
+  uint32_t struct_size;              /* sizeof(ddmi_neighbor_graph_cfg) the caller was built against                        */
+  int32_t n_nodes;                   /* N: rows of pos                                                                      */
+  int32_t n_sets;                    /* G                                                                                   */
+  int32_t max_neighbors;             /* cap of every set without set_max_neighbors; 0 = 1000                                */
+  float cutoff;                      /* cutoff of every set without set_cutoff                                              */
+  int64_t capacity;                  /* columns of edge_index                                                               */
+  const float* pos;                  /* device [N, 3]                                                                       */
+  const int32_t* ptr;                /* HOST [G + 1]                                                                        */
+  const float* set_cutoff;           /* HOST [G] or NULL: one cutoff per set                                                */
+  const int32_t* set_max_neighbors;  /* HOST [G] or NULL: one cap per set                                                   */
+  int32_t* deg;                      /* device [N] or NULL                                                                  */
+  int32_t* offsets;                  /* device [N + 1] or NULL                                                              */
+  int64_t* edge_index;               /* device [2, capacity] or NULL                                                        */
+  int32_t* n_edges;                  /* device [1] or NULL                                                                  */
+} ddmi_neighbor_graph_cfg;
+int ddmi_neighbor_graph(ddmi_model* m, const ddmi_neighbor_graph_cfg* cfg, ddmi_stream stream);
+
 /* Introspection for tests and profiling: copy a named internal buffer to the host.
  * ddmi_debug_shape returns the element count and up to 4 dims; names are listed in DESIGN.md. */
 int ddmi_debug_shape(ddmi_model* m, const char* name, int64_t shape[4], int* ndim, int* is_int);
