@@ -92,6 +92,8 @@ void ddmi_destroy(ddmi_model* h) {
   for (hipEvent_t e : m.ev_pipe) (void)hipEventDestroy(e);
   if (m.nbr_ev) { (void)hipEventSynchronize(m.nbr_ev); (void)hipEventDestroy(m.nbr_ev); }
   if (m.nbr_host) (void)hipHostFree(m.nbr_host);
+  if (m.match_ev) { (void)hipEventSynchronize(m.match_ev); (void)hipEventDestroy(m.match_ev); }
+  if (m.match_host) (void)hipHostFree(m.match_host);
   delete h;
 }
 
@@ -268,6 +270,22 @@ int ddmi_neighbor_graph(ddmi_model* h, const ddmi_neighbor_graph_cfg* cfg, ddmi_
     DDMI_REQUIRE(cfg->n_nodes > 0 && cfg->n_sets > 0, DDMI_ERR_ARG, "ddmi_neighbor_graph_cfg: n_nodes and n_sets must be positive");
     DDMI_CHECK_HIP(hipSetDevice(h->m.device));
     neighbor_graph(h->m, *cfg, (hipStream_t)s);
+  });
+}
+
+int ddmi_match_conformer(ddmi_model* h, const ddmi_match_cfg* cfg, ddmi_stream s) {
+  return guard([&] {
+    DDMI_REQUIRE(h && cfg, DDMI_ERR_ARG, "null argument");
+    DDMI_REQUIRE(cfg->struct_size == sizeof(ddmi_match_cfg), DDMI_ERR_ARG, "ddmi_match_cfg.struct_size does not match this library");
+    DDMI_REQUIRE(cfg->start && cfg->target && cfg->lig_ptr && cfg->tor_ptr, DDMI_ERR_ARG,
+                 "ddmi_match_cfg: start, target, lig_ptr and tor_ptr are required");
+    DDMI_REQUIRE(cfg->n_jobs >= 1, DDMI_ERR_ARG, "ddmi_match_cfg: n_jobs must be positive");
+    DDMI_REQUIRE(cfg->popsize >= 1 && cfg->maxiter >= 0, DDMI_ERR_ARG, "ddmi_match_cfg: popsize must be positive and maxiter not negative");
+    DDMI_REQUIRE(cfg->tol >= 0.f, DDMI_ERR_ARG, "ddmi_match_cfg: tol must not be negative");   // (false for NaN)
+    DDMI_REQUIRE(cfg->n_init >= 0 && (cfg->n_init == 0 || cfg->init_angles || cfg->tor_ptr[cfg->n_jobs] == 0), DDMI_ERR_ARG,
+                 "ddmi_match_cfg: n_init must not be negative, and n_init > 0 needs init_angles");
+    DDMI_CHECK_HIP(hipSetDevice(h->m.device));
+    match_conformer(h->m, *cfg, (hipStream_t)s);
   });
 }
 

@@ -18,6 +18,7 @@
 
 #include "jacobi4.h"
 #include "kernels.h"
+#include "wave_f64.h"
 
 namespace ddmi {
 
@@ -29,15 +30,6 @@ __device__ __forceinline__ unsigned wave_min_u32(unsigned v) {
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) {
     const unsigned o = (unsigned)__shfl_xor((int)v, m, 64);
-    v = o < v ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    const unsigned hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), m, 64), lo = (unsigned)__shfl_xor((int)(unsigned)v, m, 64);
-    const unsigned long long o = ((unsigned long long)hi << 32) | lo;
     v = o < v ? o : v;
   }
   return v;
@@ -233,34 +225,7 @@ void launch_pose_metrics(const PoseMetricsArgs& a, hipStream_t s) {
 //                      reflects) and t = cb - R ca, so that R a_j + t ~ b_j; R and t are stored as float32.  m = 1 gives the identity.
 //                      Where the largest eigenvalue is degenerate (m = 2, collinear atoms: any rotation about the common axis) every
 //                      maximiser is a correct answer and the one returned is the one the Jacobi sweeps arrive at.
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
-    const unsigned hi = (unsigned)__shfl_xor((int)(unsigned)(b >> 32), m, 64), lo = (unsigned)__shfl_xor((int)(unsigned)b, m, 64);
-    v += __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-  }
-  return v;
-}
-
-// one wave: c[0..2] = the centroid of the m atoms atom(j), c[3] = sum_j |atom(j) - centroid|^2
-template <class Atom> __device__ __forceinline__ void fit_center(const Atom& atom, int m, int lane, double* c) {
-  double sx = 0.0, sy = 0.0, sz = 0.0;
-  for (int j = lane; j < m; j += 64) {
-    float x, y, z;
-    atom(j, x, y, z);
-    sx += (double)x; sy += (double)y; sz += (double)z;
-  }
-  const double cx = wave_sum_f64(sx) / (double)m, cy = wave_sum_f64(sy) / (double)m, cz = wave_sum_f64(sz) / (double)m;
-  double g = 0.0;
-  for (int j = lane; j < m; j += 64) {
-    float x, y, z;
-    atom(j, x, y, z);
-    const double dx = (double)x - cx, dy = (double)y - cy, dz = (double)z - cz;
-    g = fma(dz, dz, fma(dy, dy, fma(dx, dx, g)));
-  }
-  c[0] = cx; c[1] = cy; c[2] = cz; c[3] = wave_sum_f64(g);
-}
+// (wave_sum_f64, wave_min_u64 and fit_center -- the centroid and the centred square sum of one set of atoms -- live in wave_f64.h)
 // one wave: M [3][3] = sum_j (a_j - ca)(b_j - cb)^T with b_j = the reference atom pr[j] (pr == nullptr: j)
 template <bool STAGED> __device__ __forceinline__ void fit_cross(const MetView<STAGED>& v, const int* __restrict__ pr, int m, int lane,
                                                                  const double* ca, const double* cb, double* M) {

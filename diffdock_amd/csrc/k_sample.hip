@@ -8,32 +8,12 @@
 //                       (utils/geometry.py:246-276).  The optimal proper rotation is obtained
 //                       from Horn's quaternion eigenproblem (float64 Jacobi) instead of an SVD
 //                       with reflection fix: the same minimiser, no 3x3 SVD kernel needed.
+#include "axis_angle.h"
 #include "jacobi4.h"
 #include "kernels.h"
+#include "philox.h"
 
 namespace ddmi {
-
-// ------------------------------------------------------------------ counter-based RNG
-__device__ __forceinline__ void philox4x32(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
-                                           unsigned* out) {
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1;
-    const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-// standard normal keyed by (seed, sample, step, component)
-__device__ __forceinline__ float normal_draw(unsigned long long seed, long long sample, int step, int comp) {
-  unsigned o[4];
-  philox4x32((unsigned)sample, (unsigned)((unsigned long long)sample >> 32), (unsigned)step, (unsigned)comp,
-             (unsigned)seed, (unsigned)(seed >> 32), o);
-  const float u1 = ((float)(o[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-  const float u2 = ((float)(o[1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-  return sqrtf(-2.0f * logf(u1)) * cosf(6.283185307179586f * u2);
-}
 
 // test entry points: the generator exactly as k_perturb uses it
 __global__ void k_debug_philox(const unsigned* __restrict__ ctr, const unsigned* __restrict__ key, int n, unsigned* __restrict__ out) {
@@ -207,17 +187,6 @@ void launch_fill_times(float* t, int B, float t_tr, float t_rot, float t_tor, hi
 }
 
 // ------------------------------------------------------------------ conformer update
-__device__ __forceinline__ void axis_angle_to_matrix(float ax, float ay, float az, float* R) {
-  const float angle = sqrtf(ax * ax + ay * ay + az * az);
-  const float half = 0.5f * angle;
-  const float s = fabsf(angle) < 1e-6f ? 0.5f - (angle * angle) / 48.f : sinf(half) / angle;
-  const float r = cosf(half), i = ax * s, j = ay * s, k = az * s;
-  const float two_s = 2.0f / (r * r + i * i + j * j + k * k);
-  R[0] = 1 - two_s * (j * j + k * k); R[1] = two_s * (i * j - k * r); R[2] = two_s * (i * k + j * r);
-  R[3] = two_s * (i * j + k * r); R[4] = 1 - two_s * (i * i + k * k); R[5] = two_s * (j * k - i * r);
-  R[6] = two_s * (i * k - j * r); R[7] = two_s * (j * k + i * r); R[8] = 1 - two_s * (i * i + j * j);
-}
-
 // one graph (64 threads): p [Nl][3] in place; tr / rot [3] and tor [R] (or nullptr) are the graph's updates, rot_u / rot_v
 // graph-local atom indices, mask_rotate its [R][Nl] block.  smem holds 6 * Nl + 16 floats.  rp: nullptr, or the graph's [Nl][3]
 // block of a record row (ddmi_set_sample_record) that receives the final coordinates as well.

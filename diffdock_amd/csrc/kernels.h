@@ -431,4 +431,32 @@ struct NeighborArgs {
 void launch_neighbor_count(const NeighborArgs& a, hipStream_t s);
 void launch_neighbor_fill(const NeighborArgs& a, hipStream_t s);
 
+// ddmi_match_conformer (k_match.hip): differential evolution over the torsion angles of a ragged batch of jobs, one workgroup of
+// MATCH_WAVES waves per job, every generation inside the one launch.  lig_ptr / tor_ptr [J + 1], mask_off / job_ids / pop_off [J] are
+// DEVICE tables here (the host entry point stages them); job_list [count] names the jobs of this launch.  A job of n atoms and R
+// rotatable bonds has a population of P = match_population(..) rows; two copies of it (this generation and the next) and its energies,
+// match_pop_words(P, R) 32-bit words, live in LDS when match_lds_bytes(n, R, P, true) <= MATCH_LDS_BYTES and at pop_ws + pop_off[job]
+// otherwise -- the same arithmetic in the same order either way.  Limits: n <= MATCH_MAX_ATOMS (the working conformer of every wave is
+// in LDS), R <= MATCH_MAX_TORSIONS (one bit of a 64-bit word per bond and atom, one lane per angle), P <= MATCH_MAX_POP.
+constexpr int MATCH_WAVES = 8, MATCH_MAX_ATOMS = 256, MATCH_MAX_TORSIONS = 64, MATCH_MAX_POP = 1 << 20, MATCH_LDS_BYTES = 64 * 1024;
+__host__ __device__ inline long match_population(int R, int popsize, int n_init) {
+  if (R == 0) return n_init > 1 ? n_init : 1;
+  long P = (long)popsize * R;
+  if (P < 5) P = 5;
+  return P < n_init ? n_init : P;
+}
+__host__ __device__ inline size_t match_pop_words(long P, int R) { return 2 * (size_t)P * R + (size_t)P; }
+__host__ __device__ inline size_t match_lds_bytes(int n, int R, long P, bool pop_lds) {
+  return 8 * (size_t)(16 + 3 * MATCH_WAVES + n) + 4 * (size_t)(6 * n + 3 * n * MATCH_WAVES + 64 * MATCH_WAVES + 2 * R) +
+         (pop_lds ? 4 * match_pop_words(P, R) : 0);
+}
+struct MatchArgs {
+  const int* job_list; const int *lig_ptr, *tor_ptr; const long long *mask_off, *job_ids, *pop_off;
+  const float *start, *target; const int *rot_u, *rot_v; const unsigned char* mask_rotate;
+  const float* init_angles; int n_init, popsize, maxiter; float tol; unsigned long long seed;
+  float* pop_ws;
+  float *angles, *rmsd, *pos, *init_energy, *best_history; int* n_generations;
+};
+void launch_match(const MatchArgs& a, int count, bool pop_lds, size_t smem, hipStream_t s);
+
 }  // namespace ddmi

@@ -141,6 +141,8 @@ struct Model {
   DevicePool mpool; void* metrics_ws = nullptr; size_t metrics_ws_bytes = 0;   // ddmi_pose_metrics / ddmi_pose_fit scratch: grows, never shrinks
   DevicePool npool; void* nbr_ws = nullptr; size_t nbr_ws_bytes = 0;           // ddmi_neighbor_graph scratch: grows, never shrinks
   int32_t* nbr_host = nullptr; size_t nbr_host_words = 0; hipEvent_t nbr_ev = nullptr;   // pinned staging of its per-set table
+  DevicePool xpool; void* match_ws = nullptr; size_t match_ws_bytes = 0;       // ddmi_match_conformer scratch: grows, never shrinks
+  char* match_host = nullptr; size_t match_host_bytes = 0; hipEvent_t match_ev = nullptr;   // pinned staging of its per-job tables
   struct Cx;  // cx.h
   std::shared_ptr<Cx> cx;
   std::map<std::string, DebugEntry> debug;
@@ -188,5 +190,7 @@ void pose_metrics(Model& m, const ddmi_pose_metrics_cfg& mc, hipStream_t s);
 void pose_fit(Model& m, const ddmi_pose_fit_cfg& fc, hipStream_t s);
 // capped neighbour lists of a ragged batch of point sets (process_mols.py:171-192, :207-228); needs no complex
 void neighbor_graph(Model& m, const ddmi_neighbor_graph_cfg& nc, hipStream_t s);
+// conformer matching of a ragged batch of jobs (datasets/conformer_matching.py); needs no complex
+void match_conformer(Model& m, const ddmi_match_cfg& mc, hipStream_t s);
 
 }  // namespace ddmi

@@ -260,6 +260,83 @@ void neighbor_graph(Model& m, const ddmi_neighbor_graph_cfg& nc, hipStream_t s) 
   if (nc.edge_index) launch_neighbor_fill(a, s);
 }
 
+// ddmi_match_conformer: the per-job tables (ptrs, mask offsets, job ids, the place of a population that does not fit LDS, the job lists
+// of the two launches) are checked on the host and ride through a pinned staging buffer as the table of neighbor_graph does -- consumed
+// before this returns, nothing waits for the stream.  Jobs whose population fits LDS run in one launch, the others in a second one with
+// their populations in the handle's scratch: the same kernel arithmetic either way.
+void match_conformer(Model& m, const ddmi_match_cfg& mc, hipStream_t s) {
+  const int J = mc.n_jobs;
+  DDMI_REQUIRE(mc.lig_ptr[0] == 0 && mc.tor_ptr[0] == 0, DDMI_ERR_ARG, "ddmi_match_cfg: lig_ptr and tor_ptr must start at 0");
+  bool torsions = false;
+  for (int j = 0; j < J; ++j) {
+    DDMI_REQUIRE(mc.tor_ptr[j + 1] >= mc.tor_ptr[j] && mc.lig_ptr[j + 1] >= mc.lig_ptr[j], DDMI_ERR_ARG, "ddmi_match_cfg: a ptr decreases");
+    DDMI_REQUIRE(mc.lig_ptr[j + 1] > mc.lig_ptr[j], DDMI_ERR_ARG, "ddmi_match_cfg: a job of 0 atoms");
+    torsions = torsions || mc.tor_ptr[j + 1] > mc.tor_ptr[j];
+  }
+  DDMI_REQUIRE(!torsions || (mc.rot_u && mc.rot_v && mc.mask_rotate), DDMI_ERR_ARG,
+               "ddmi_match_cfg: rotatable bonds need rot_u, rot_v and mask_rotate");
+  // layout of the staged tables: int lig_ptr [J + 1], tor_ptr [J + 1], list_lds [J], list_ws [J]; then 64-bit mask_off, job_ids, pop_off [J]
+  const size_t ints = round_up(4 * (size_t)J + 2, 2), tab_bytes = ints * sizeof(int32_t) + 3 * (size_t)J * sizeof(int64_t);
+  if (tab_bytes > m.match_host_bytes) {
+    if (m.match_ev) DDMI_CHECK_HIP(hipEventSynchronize(m.match_ev));
+    else DDMI_CHECK_HIP(hipEventCreate(&m.match_ev));
+    if (m.match_host) { (void)hipHostFree(m.match_host); m.match_host = nullptr; m.match_host_bytes = 0; }
+    DDMI_CHECK_HIP(hipHostMalloc(reinterpret_cast<void**>(&m.match_host), tab_bytes));
+    m.match_host_bytes = tab_bytes;
+  } else {
+    DDMI_CHECK_HIP(hipEventSynchronize(m.match_ev));
+  }
+  int32_t* h_lig = reinterpret_cast<int32_t*>(m.match_host);
+  int32_t *h_tor = h_lig + J + 1, *h_lds = h_tor + J + 1, *h_ws = h_lds + J;
+  int64_t* h_off = reinterpret_cast<int64_t*>(m.match_host + ints * sizeof(int32_t));
+  int64_t *h_ids = h_off + J, *h_pop = h_ids + J;
+  int n_lds = 0, n_ws = 0;
+  size_t smem_lds = 0, smem_ws = 0, pop_words = 0;
+  int64_t mask_at = 0;
+  for (int j = 0; j < J; ++j) {
+    const int n = mc.lig_ptr[j + 1] - mc.lig_ptr[j], R = mc.tor_ptr[j + 1] - mc.tor_ptr[j];
+    DDMI_REQUIRE(n <= MATCH_MAX_ATOMS && R <= MATCH_MAX_TORSIONS, DDMI_ERR_CAPACITY,
+                 "ddmi_match_conformer: job " + std::to_string(j) + " has " + std::to_string(n) + " atoms and " + std::to_string(R) +
+                     " rotatable bonds; the limits are " + std::to_string(MATCH_MAX_ATOMS) + " and " + std::to_string(MATCH_MAX_TORSIONS));
+    const long P = match_population(R, mc.popsize, mc.n_init);
+    DDMI_REQUIRE(P <= MATCH_MAX_POP, DDMI_ERR_CAPACITY, "ddmi_match_conformer: a population above 2^20 members");
+    h_lig[j] = mc.lig_ptr[j]; h_tor[j] = mc.tor_ptr[j];
+    h_off[j] = mc.mask_off ? mc.mask_off[j] : mask_at;
+    mask_at += (int64_t)R * n;
+    h_ids[j] = mc.job_ids ? mc.job_ids[j] : j;
+    const size_t need = match_lds_bytes(n, R, P, true);
+    if (need <= (size_t)MATCH_LDS_BYTES) {
+      h_pop[j] = 0; h_lds[n_lds++] = j; smem_lds = std::max(smem_lds, need);
+    } else {
+      h_pop[j] = (int64_t)pop_words; pop_words += match_pop_words(P, R);
+      h_ws[n_ws++] = j; smem_ws = std::max(smem_ws, match_lds_bytes(n, R, P, false));
+    }
+  }
+  h_lig[J] = mc.lig_ptr[J]; h_tor[J] = mc.tor_ptr[J];
+  const size_t tab_dev = round_up((long)tab_bytes, 256), bytes = tab_dev + pop_words * sizeof(float);
+  if (bytes > m.match_ws_bytes) {   // (hipFree waits for the device: kernels of an earlier call keep their memory)
+    m.xpool.release();
+    m.match_ws = nullptr; m.match_ws_bytes = 0;
+    m.match_ws = m.xpool.alloc_bytes(bytes);
+    m.match_ws_bytes = bytes;
+  }
+  char* ws = reinterpret_cast<char*>(m.match_ws);
+  DDMI_CHECK_HIP(hipMemcpyAsync(ws, m.match_host, tab_bytes, hipMemcpyHostToDevice, s));
+  DDMI_CHECK_HIP(hipEventRecord(m.match_ev, s));
+  MatchArgs a{};
+  a.lig_ptr = reinterpret_cast<const int*>(ws); a.tor_ptr = a.lig_ptr + J + 1;
+  a.mask_off = reinterpret_cast<const long long*>(ws + ints * sizeof(int32_t)); a.job_ids = a.mask_off + J; a.pop_off = a.job_ids + J;
+  a.start = mc.start; a.target = mc.target; a.rot_u = mc.rot_u; a.rot_v = mc.rot_v; a.mask_rotate = mc.mask_rotate;
+  a.init_angles = mc.init_angles; a.n_init = mc.n_init; a.popsize = mc.popsize; a.maxiter = mc.maxiter; a.tol = mc.tol; a.seed = mc.seed;
+  a.pop_ws = reinterpret_cast<float*>(ws + tab_dev);
+  a.angles = mc.angles; a.rmsd = mc.rmsd; a.pos = mc.pos; a.init_energy = mc.init_energy; a.best_history = mc.best_history;
+  a.n_generations = mc.n_generations;
+  a.job_list = a.tor_ptr + J + 1;
+  launch_match(a, n_lds, true, smem_lds, s);
+  a.job_list += J;
+  launch_match(a, n_ws, false, smem_ws, s);
+}
+
 void sample(Model& m, float* lig_pos, const ddmi_sample_cfg& sc, hipStream_t s) {
   DDMI_REQUIRE(m.has_complex, DDMI_ERR_STATE, "ddmi_set_complex must precede ddmi_sample");
   check_sample_cfg(m, sc);

@@ -24,6 +24,8 @@ ones from its valence model).  The ESM language-model embeddings (`lm_embeddings
 """
 from __future__ import annotations
 
+import os
+
 import numpy as np
 import torch
 
@@ -360,7 +362,8 @@ def transformation_mask(n_atoms, edge_index):
 
 
 def complex_graph(pdb_path, sdf_path, receptor_radius=15.0, c_alpha_max_neighbors=24, lm_embeddings=None, atom_features=None,
-                  lm_dim=1280, name=None, all_atoms=False, atom_radius=5.0, atom_max_neighbors=8, model=None) -> HeteroData:
+                  lm_dim=1280, name=None, all_atoms=False, atom_radius=5.0, atom_max_neighbors=8, model=None, conformers=None,
+                  matching_popsize=20, matching_maxiter=20, matching_tries=None) -> HeteroData:
     """HeteroData with the schema of the reference's preprocessed complex: receptor C-alpha graph, ligand
     heavy-atom graph with rotatable-bond masks, both centred on the receptor's C-alpha centroid (`original_center`,
     datasets/pdbbind.py get_complex).  `lm_embeddings` [n_res, 1280] and `atom_features` [n_lig, 16] are the external
@@ -370,7 +373,12 @@ def complex_graph(pdb_path, sdf_path, receptor_radius=15.0, c_alpha_max_neighbor
     at most `atom_max_neighbors`) and `atom_rec_contact`.  With `model=` (an MIScoreModel) BOTH neighbour graphs, residues and
     atoms, come from one ddmi_neighbor_graph call on the model's device (float32 direct differences, `neighbor_graph`); without
     it the residue graph is `receptor_graph` (the reference's torch.cdist arithmetic) and the atom graph the host restatement of
-    `neighbor_graph`."""
+    `neighbor_graph`.
+    `conformers` (arrays [T, n_lig, 3] or SDF/MOL paths of the same molecule in another conformation; generating them needs RDKit
+    and stays an input) switches conformer matching on, as get_lig_graph_with_matching(matching=True, keep_original=True) does:
+    g['ligand'].orig_pos is the file's pose, g['ligand'].pos the matched conformer of the best of `matching_tries` tries in that
+    frame, centred as above, and g.rmsd_matching its distance (`diffdock_amd.matching`; on the device with `model=`, through scipy
+    without).  Without `conformers` nothing of this is set."""
     rc, rtype, _ = read_pdb_calpha(pdb_path)
     lc, z, bonds = read_sdf(sdf_path)
     g = HeteroData()
@@ -417,6 +425,18 @@ def complex_graph(pdb_path, sdf_path, receptor_radius=15.0, c_alpha_max_neighbor
     mask_edges, mask_rotate = transformation_mask(len(z), ei)
     g["ligand"].x = torch.from_numpy(feats)
     g["ligand"].pos = torch.from_numpy(lc.astype(np.float32)) - center
+    if conformers is not None:      # get_lig_graph_with_matching(matching=True, keep_original=True), process_mols.py:323-384
+        from .matching import match_conformers, match_conformers_host
+        starts = [read_sdf(c)[0] if isinstance(c, (str, os.PathLike)) else np.asarray(c, dtype=np.float64) for c in conformers] \
+            if isinstance(conformers, (list, tuple)) else np.asarray(conformers, dtype=np.float64).reshape(-1, len(z), 3)
+        starts = np.stack([np.asarray(s, dtype=np.float32).reshape(len(z), 3) for s in starts])
+        rot = ei.T[mask_edges]
+        job = ((rot[:, 0], rot[:, 1], mask_rotate), starts, g["ligand"].pos.numpy())     # matched in the centred frame
+        kw = dict(popsize=matching_popsize, maxiter=matching_maxiter, tries=matching_tries)
+        best = match_conformers_host([job], **kw)[0] if model is None else match_conformers([job], model, **kw)[0]
+        g["ligand"].orig_pos = lc                                                      # the file's pose, as the reference keeps it
+        g["ligand"].pos = torch.as_tensor(best["pos"]).detach().to("cpu", torch.float32)
+        g.rmsd_matching = float(best["rmsd"])
     g["ligand"].edge_mask = torch.from_numpy(mask_edges)
     g["ligand"].mask_rotate = [mask_rotate]
     g["ligand", "lig_bond", "ligand"].edge_index = torch.from_numpy(ei)

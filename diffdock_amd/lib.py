@@ -165,6 +165,14 @@ class NeighborGraphCfg(C.Structure):   # ddmi_neighbor_graph_cfg (include/ddmi.h
                [(n, C.c_void_p) for n in ("pos", "ptr", "set_cutoff", "set_max_neighbors", "deg", "offsets", "edge_index", "n_edges")]
 
 
+class MatchCfg(C.Structure):   # ddmi_match_cfg (include/ddmi.h)
+    _fields_ = [("struct_size", C.c_uint32), ("n_jobs", C.c_int32), ("popsize", C.c_int32), ("maxiter", C.c_int32),
+                ("n_init", C.c_int32), ("tol", C.c_float), ("seed", C.c_uint64)] + \
+               [(n, C.c_void_p) for n in ("lig_ptr", "tor_ptr", "mask_off", "job_ids", "start", "target", "rot_u", "rot_v",
+                                          "mask_rotate", "init_angles", "angles", "rmsd", "pos", "init_energy", "best_history",
+                                          "n_generations")]
+
+
 def make_config(cfg) -> Config:
     c = Config()
     for name, _ in Config._fields_:
@@ -213,6 +221,7 @@ _DECLS = {
     "ddmi_pose_metrics": (C.c_int, [C.c_void_p, C.POINTER(PoseMetricsCfg), C.c_void_p]),
     "ddmi_pose_fit": (C.c_int, [C.c_void_p, C.POINTER(PoseFitCfg), C.c_void_p]),
     "ddmi_neighbor_graph": (C.c_int, [C.c_void_p, C.POINTER(NeighborGraphCfg), C.c_void_p]),
+    "ddmi_match_conformer": (C.c_int, [C.c_void_p, C.POINTER(MatchCfg), C.c_void_p]),
     "ddmi_perturb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SampleCfg), C.c_int, C.c_void_p]),
     "ddmi_debug_shape": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "ddmi_debug_read": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -430,6 +430,67 @@ class MIScoreModel:
                     t.record_stream(torch.cuda.current_stream(dev))
         return out
 
+    def match_conformer(self, start, target, lig_ptr, tor_ptr=None, rot_u=None, rot_v=None, mask_rotate=None, popsize=15, maxiter=500,
+                        tol=0.01, seed=0, job_ids=None, init_angles=None, n_init=0):
+        """Conformer matching on the device (ddmi_match_conformer; datasets/conformer_matching.py): a ragged batch of J jobs, job j
+        owning the atoms lig_ptr[j]:lig_ptr[j + 1] of `start` / `target` [sum n, 3] and the rotatable bonds tor_ptr[j]:tor_ptr[j + 1]
+        of `rot_u` / `rot_v` (job-local atom indices); `mask_rotate` holds every job's [R_j, n_j] block, flattened, in job order
+        (`matching.torsion_table` builds the three).  `init_angles` [sum_j n_init * R_j] gives job j's first n_init population rows;
+        they must lie in [-pi, pi] and are used as given, neither clamped nor wrapped.
+        Returns a dict of device tensors: angles [sum R], rmsd [J], pos [sum n, 3] (the matched conformer in the frame of target),
+        best_history [J, maxiter + 1], n_generations [J] and, with n_init, init_energy [J, n_init].  Needs no complex and does not
+        synchronise; the result of a job depends on its inputs, its `job_ids` entry (default: its index) and `seed` alone."""
+        dev = self.device
+        start = torch.as_tensor(start).to(dev, torch.float32).contiguous()
+        target = torch.as_tensor(target).to(dev, torch.float32).contiguous()
+        lig = np.ascontiguousarray(np.asarray(lig_ptr).reshape(-1), dtype=np.int32)
+        J = len(lig) - 1
+        tor = np.zeros(J + 1, dtype=np.int32) if tor_ptr is None else np.ascontiguousarray(np.asarray(tor_ptr).reshape(-1), dtype=np.int32)
+        if len(tor) != J + 1:
+            raise ValueError(f"tor_ptr: [{J + 1}] expected, got {len(tor)}")
+        N, nT = (int(lig[-1]), int(tor[-1])) if J >= 1 else (0, 0)
+        if start.dim() != 2 or start.shape[1] != 3 or (J >= 1 and start.shape[0] != N):
+            raise ValueError(f"start: [{N}, 3] expected, got {tuple(start.shape)}")
+        if target.shape != start.shape:
+            raise ValueError(f"target: {tuple(start.shape)} expected, got {tuple(target.shape)}")
+        i32 = lambda t: None if t is None else torch.as_tensor(t).to(dev, torch.int32).reshape(-1).contiguous()
+        rot_u, rot_v = i32(rot_u), i32(rot_v)
+        for name, t in (("rot_u", rot_u), ("rot_v", rot_v)):
+            if t is not None and t.numel() != nT:
+                raise ValueError(f"{name}: [{nT}] expected, got {t.numel()}")
+        mask_bytes = int(np.sum(np.diff(tor.astype(np.int64)) * np.diff(lig.astype(np.int64)))) if J >= 1 else 0
+        if mask_rotate is not None:
+            mask_rotate = torch.as_tensor(mask_rotate).to(dev, torch.uint8).reshape(-1).contiguous()
+            if mask_rotate.numel() != mask_bytes:
+                raise ValueError(f"mask_rotate: {mask_bytes} bytes (every job's [R, n] block) expected, got {mask_rotate.numel()}")
+        n_init = int(n_init)
+        if init_angles is not None:
+            init_angles = torch.as_tensor(init_angles).to(dev, torch.float32).reshape(-1).contiguous()
+            if n_init < 1 or init_angles.numel() != n_init * nT:
+                raise ValueError(f"init_angles: n_init >= 1 and {max(n_init, 0) * nT} angles expected, got n_init = {n_init}, {init_angles.numel()}")
+        ids = None if job_ids is None else np.ascontiguousarray(np.asarray(job_ids).reshape(-1), dtype=np.int64)
+        if ids is not None and len(ids) != J:
+            raise ValueError(f"job_ids: [{J}] expected, got {len(ids)}")
+        H = max(int(maxiter), 0) + 1
+        f = lambda *shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=dev)
+        out = dict(angles=f(nT), rmsd=f(max(J, 0)), pos=f(N, 3), best_history=f(max(J, 0), H), n_generations=f(max(J, 0), dtype=torch.int32))
+        if n_init > 0:
+            out["init_energy"] = f(max(J, 0), n_init)
+        mc = _lib.MatchCfg()
+        mc.struct_size = C.sizeof(_lib.MatchCfg)
+        mc.n_jobs, mc.popsize, mc.maxiter, mc.n_init, mc.tol, mc.seed = J, int(popsize), int(maxiter), n_init, float(tol), int(seed)
+        mc.lig_ptr, mc.tor_ptr = lig.ctypes.data, tor.ctypes.data
+        mc.job_ids = None if ids is None else ids.ctypes.data
+        inputs = dict(start=start, target=target, rot_u=rot_u, rot_v=rot_v, mask_rotate=mask_rotate, init_angles=init_angles)
+        for name, t in list(inputs.items()) + list(out.items()):
+            setattr(mc, name, None if t is None or t.numel() == 0 else t.data_ptr())
+        _lib.check(self.lib, self.lib.ddmi_match_conformer(self._h, C.byref(mc), self._stream()))
+        if dev.type == "cuda":   # converted copies of the inputs must outlive the enqueued kernels
+            for t in inputs.values():
+                if t is not None:
+                    t.record_stream(torch.cuda.current_stream(dev))
+        return out
+
     def pose_metrics(self, pos, ref, perm=None, atom_index=None, points=None, per_ref=False):
         """Judge poses on the device (ddmi_pose_metrics; evaluate.py:474-505): `pos` [P, n, 3] or a trajectory [T, P, n, 3], `ref`
         [K, m, 3] (or [m, 3]) known poses, `perm` int [S, m] graph isomorphisms as metrics.isomorphisms returns them (None = the

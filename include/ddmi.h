@@ -471,6 +471,67 @@ typedef struct ddmi_neighbor_graph_cfg {
 } ddmi_neighbor_graph_cfg;
 int ddmi_neighbor_graph(ddmi_model* m, const ddmi_neighbor_graph_cfg* cfg, ddmi_stream stream);
 
+/* Conformer matching -- datasets/conformer_matching.py (optimize_rotatable_bonds), run in front of every evaluation and training set
+ * by get_lig_graph_with_matching (datasets/process_mols.py:323-384): search the torsion angles of a generated conformer for the
+ * conformer closest to the known pose.  A ragged batch of J independent jobs (one ligand, one start conformer, one known pose each);
+ * job j owns atoms lig_ptr[j] .. lig_ptr[j + 1] and rotatable bonds tor_ptr[j] .. tor_ptr[j + 1].
+ * Objective: E(theta) = the minimised RMSD between torsions(start, theta) and target.  torsions is the loop of ddmi_randomize_position
+ * (bonds in edge order, float32, an angle of exactly 0 skipped, no re-alignment); the RMSD is the formula of ddmi_pose_fit with the
+ * identity permutation, in float64 on the float32 coordinates, with its atol rule.  The reference's SetDihedralRad sets absolute
+ * dihedrals; the angles here are RELATIVE to the start conformer -- both cover a full period per bond, so the same conformers are
+ * reachable.  AlignMol's identity atom map and proper rotation hold here as well.
+ * Optimiser: differential evolution as scipy runs it for the reference (best1bin, mutation (0.5, 1) dithered per generation,
+ * recombination 0.8, P = max(5, popsize * R, n_init) members, re-draw of a component that leaves [-pi, pi], stop when
+ * std(E) <= tol * |mean(E)|; tol = 0 never stops early), with three deliberate differences: updating is generation-synchronous
+ * (scipy's updating='deferred': every trial is built from the previous generation), row 0 of the initial population is all zeros when
+ * the caller gives no rows (the result is never worse than the unmatched conformer), and there is no L-BFGS-B polish.
+ * Draws: the library's Philox4x32-10 block with key = seed and counter (job id low word, job id high word, generation, c3):
+ *   generation 0xffffffff (no generation has it), c3 = i << 6 | (j >> 2), word j & 3   angle j of member i of the initial population:
+ *                                                         u = ((word >> 8) + 0.5) / 2^24, angle = (2u - 1) pi, as ddmi_randomize_position
+ *   generation g = 1 .. maxiter, c3 = 0xffffffff, word 0          F = 0.5 + 0.5 (word >> 8) / 2^24
+ *   generation g, c3 = i << 6                                      trial i: r1 = word 0 mod (P - 1), stepped over i; r2 = word 1 mod (P - 2),
+ *                                                                  stepped over the lower, then the higher of (i, r1); jrand = word 2 mod R
+ *   generation g, c3 = i << 6 | (1 + (j >> 2)), word j & 3         u_j = ((word >> 8) + 0.5) / 2^24: component j crosses where u_j < 0.8
+ *   generation g, c3 = i << 6 | (17 + (j >> 2)), word j & 3        the re-draw of a component outside the box, the angle formula above
+ * One kernel launch per call runs every generation: one workgroup per job, one wave per evaluation, no atomics, no host synchronisation
+ * (the HOST arrays are consumed before the call returns); a job's result depends on its inputs, its job id and the seed alone.
+ * Scratch belongs to the handle and only grows; the handle gives the device, the stream order and the error text.
+ * Precondition: the rows of init_angles lie in [-pi, pi].  They enter the population as given (init_energy is E of exactly these rows)
+ * and are neither clamped nor wrapped: a row outside the box may win and is then returned in `angles` outside the box.
+ * Edge behaviour: a job with no rotatable bond is legal (rmsd = the plain fit of start on target, pos = the moved start, no
+ * generations); maxiter = 0 returns the best of the initial population.  rot_u / rot_v outside a job are clamped into it.
+ * DDMI_ERR_ARG: struct_size mismatch; NULL start / target / lig_ptr / tor_ptr; n_jobs < 1; a decreasing ptr or ptr[0] != 0; a job of 0
+ * atoms; rotatable bonds without rot_u / rot_v / mask_rotate; popsize < 1; maxiter < 0; tol < 0 or NaN; n_init < 0 or n_init > 0 without
+ * init_angles (a batch without any rotatable bond has no angles and needs none).  DDMI_ERR_CAPACITY: a job of more than 256 atoms or 64 rotatable bonds, a population above 2^20 members. */
+typedef struct ddmi_match_cfg {
+  uint32_t struct_size;        /* sizeof(ddmi_match_cfg) the caller was built against                                            */
+  int32_t n_jobs;              /* J                                                                                              */
+  int32_t popsize;             /* evaluate.py: 40, confidence/dataset.py and training: 20, the reference function's default: 15 */
+  int32_t maxiter;             /* generations; 40 / 20 / 500 as above                                                            */
+  int32_t n_init;              /* rows of init_angles per job; 0 without                                                         */
+  float tol;                   /* scipy's default 0.01                                                                           */
+  uint64_t seed;
+  const int32_t* lig_ptr;      /* HOST [J + 1]                                                                                   */
+  const int32_t* tor_ptr;      /* HOST [J + 1]                                                                                   */
+  const int64_t* mask_off;     /* HOST [J]: byte offset of job j's [R_j, n_j] block in mask_rotate, or NULL (blocks in job order) */
+  const int64_t* job_ids;      /* HOST [J] or NULL (= 0..J-1): the job's word of the draw counter                                */
+  const float* start;          /* device [sum n, 3]                                                                              */
+  const float* target;         /* device [sum n, 3]                                                                              */
+  const int32_t* rot_u;        /* device [sum R]: job-local atom indices of the bond (u, v); the mask row turns about v          */
+  const int32_t* rot_v;        /* device [sum R]                                                                                 */
+  const uint8_t* mask_rotate;  /* device bytes: every job's [R_j, n_j] block                                                     */
+  const float* init_angles;    /* device: job j's [n_init, R_j] block at n_init * tor_ptr[j], the first rows of its population    */
+  float* angles;               /* device [sum R]: the best member                                                                */
+  float* rmsd;                 /* device [J]: E of the best member                                                               */
+  float* pos;                  /* device [sum n, 3]: torsions(start, angles) moved onto target by the rotation and translation
+                                  of its fit -- what AlignMolConformers leaves in mol_rdkit (process_mols.py:356-360)            */
+  float* init_energy;          /* device [J, n_init]: E of the caller's rows, as evaluated                                       */
+  float* best_history;         /* device [J, maxiter + 1]: the best E after the initial population and after every generation;
+                                  the final value is repeated after an early stop                                               */
+  int32_t* n_generations;      /* device [J]: generations run                                                                    */
+} ddmi_match_cfg;
+int ddmi_match_conformer(ddmi_model* m, const ddmi_match_cfg* cfg, ddmi_stream stream);
+
 /* Introspection for tests and profiling: copy a named internal buffer to the host.
  * ddmi_debug_shape returns the element count and up to 4 dims; names are listed in DESIGN.md. */
 int ddmi_debug_shape(ddmi_model* m, const char* name, int64_t shape[4], int* ndim, int* is_int);
