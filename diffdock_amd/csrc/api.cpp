@@ -58,6 +58,26 @@ Routes ddmi::resolve_routes(const ddmi_config& cfg, int n_cus) {
   return r;
 }
 
+// The prologue of the cfg-taking entry points: null check, the size of a struct that carries one (name = its type), the handle's device.
+static Model& enter(ddmi_model* h, bool args_ok) {
+  DDMI_REQUIRE(h && args_ok, DDMI_ERR_ARG, "null argument");
+  DDMI_CHECK_HIP(hipSetDevice(h->m.device));
+  return h->m;
+}
+template <class Cfg> static Model& enter(ddmi_model* h, const Cfg* cfg, const char* name, bool args_ok = true) {
+  DDMI_REQUIRE(h && cfg && args_ok, DDMI_ERR_ARG, "null argument");
+  DDMI_REQUIRE(cfg->struct_size == sizeof(Cfg), DDMI_ERR_ARG, std::string(name) + ".struct_size does not match this library");
+  return enter(h, true);
+}
+// the checks ddmi_pose_metrics_cfg and ddmi_pose_fit_cfg share
+template <class Cfg> static void check_pose_cfg(const Cfg& c, const std::string& name) {
+  DDMI_REQUIRE(c.pos && c.ref, DDMI_ERR_ARG, name + ": pos and ref are required");
+  DDMI_REQUIRE(c.n_poses > 0 && c.n_atoms > 0 && c.n_kept > 0 && c.n_refs > 0, DDMI_ERR_ARG, name + ": n_poses, n_atoms, n_kept and n_refs must be positive");
+  DDMI_REQUIRE(c.n_kept <= c.n_atoms, DDMI_ERR_ARG, name + ": n_kept > n_atoms");
+  DDMI_REQUIRE(c.atom_index || c.n_kept == c.n_atoms, DDMI_ERR_ARG, name + ": without atom_index n_kept must equal n_atoms");
+  DDMI_REQUIRE(!c.perm || c.n_perms >= 1, DDMI_ERR_ARG, name + ": perm given with n_perms < 1");
+}
+
 extern "C" {
 
 const char* ddmi_last_error(void) { return g_err.c_str(); }
@@ -90,10 +110,6 @@ void ddmi_destroy(ddmi_model* h) {
   if (m.side_stream) { (void)hipStreamSynchronize(m.side_stream); (void)hipStreamDestroy(m.side_stream); }
   for (hipEvent_t e : {m.ev_fork, m.ev_join, m.ev_cross, m.ev_terms}) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : m.ev_pipe) (void)hipEventDestroy(e);
-  if (m.nbr_ev) { (void)hipEventSynchronize(m.nbr_ev); (void)hipEventDestroy(m.nbr_ev); }
-  if (m.nbr_host) (void)hipHostFree(m.nbr_host);
-  if (m.match_ev) { (void)hipEventSynchronize(m.match_ev); (void)hipEventDestroy(m.match_ev); }
-  if (m.match_host) (void)hipHostFree(m.match_host);
   delete h;
 }
 
@@ -155,17 +171,15 @@ int ddmi_set_time_frequencies(ddmi_model* h, const float* freq, int64_t n) {
 
 int ddmi_set_complex(ddmi_model* h, const ddmi_complex* c, ddmi_stream s) {
   return guard([&] {
-    DDMI_REQUIRE(h && c, DDMI_ERR_ARG, "null argument");
-    DDMI_CHECK_HIP(hipSetDevice(h->m.device));
-    set_complex(h->m, *c, (hipStream_t)s);
+    Model& m = enter(h, c != nullptr);
+    set_complex(m, *c, (hipStream_t)s);
   });
 }
 
 int ddmi_set_batch_layout(ddmi_model* h, const ddmi_batch_layout* l, ddmi_stream s) {
   return guard([&] {
-    DDMI_REQUIRE(h && l, DDMI_ERR_ARG, "null argument");
-    DDMI_CHECK_HIP(hipSetDevice(h->m.device));
-    set_batch_layout(h->m, *l, (hipStream_t)s);
+    Model& m = enter(h, l != nullptr);
+    set_batch_layout(m, *l, (hipStream_t)s);
   });
 }
 
@@ -215,68 +229,48 @@ int ddmi_modify_conformer(ddmi_model* h, float* lig_pos, const float* tr, const 
 
 int ddmi_sample(ddmi_model* h, float* lig_pos, const ddmi_sample_cfg* cfg, ddmi_stream s) {
   return guard([&] {
-    DDMI_REQUIRE(h && lig_pos && cfg, DDMI_ERR_ARG, "null argument");
-    DDMI_CHECK_HIP(hipSetDevice(h->m.device));
-    sample(h->m, lig_pos, *cfg, (hipStream_t)s);
+    Model& m = enter(h, lig_pos && cfg);
+    sample(m, lig_pos, *cfg, (hipStream_t)s);
   });
 }
 
 int ddmi_randomize_position(ddmi_model* h, float* lig_pos, const ddmi_randomize_cfg* cfg, ddmi_stream s) {
   return guard([&] {
-    DDMI_REQUIRE(h && lig_pos && cfg, DDMI_ERR_ARG, "null argument");
-    DDMI_REQUIRE(cfg->struct_size == sizeof(ddmi_randomize_cfg), DDMI_ERR_ARG, "ddmi_randomize_cfg.struct_size does not match this library");
+    Model& m = enter(h, cfg, "ddmi_randomize_cfg", lig_pos != nullptr);
     DDMI_REQUIRE(cfg->center, DDMI_ERR_ARG, "ddmi_randomize_cfg.center is required");
-    DDMI_CHECK_HIP(hipSetDevice(h->m.device));
-    randomize_position(h->m, lig_pos, *cfg, (hipStream_t)s);
+    randomize_position(m, lig_pos, *cfg, (hipStream_t)s);
   });
 }
 
 int ddmi_pose_metrics(ddmi_model* h, const ddmi_pose_metrics_cfg* cfg, ddmi_stream s) {
   return guard([&] {
-    DDMI_REQUIRE(h && cfg, DDMI_ERR_ARG, "null argument");
-    DDMI_REQUIRE(cfg->struct_size == sizeof(ddmi_pose_metrics_cfg), DDMI_ERR_ARG, "ddmi_pose_metrics_cfg.struct_size does not match this library");
-    DDMI_REQUIRE(cfg->pos && cfg->ref, DDMI_ERR_ARG, "ddmi_pose_metrics_cfg: pos and ref are required");
-    DDMI_REQUIRE(cfg->n_poses > 0 && cfg->n_atoms > 0 && cfg->n_kept > 0 && cfg->n_refs > 0, DDMI_ERR_ARG,
-                 "ddmi_pose_metrics_cfg: n_poses, n_atoms, n_kept and n_refs must be positive");
-    DDMI_REQUIRE(cfg->n_kept <= cfg->n_atoms, DDMI_ERR_ARG, "ddmi_pose_metrics_cfg: n_kept > n_atoms");
-    DDMI_REQUIRE(cfg->atom_index || cfg->n_kept == cfg->n_atoms, DDMI_ERR_ARG, "ddmi_pose_metrics_cfg: without atom_index n_kept must equal n_atoms");
-    DDMI_REQUIRE(!cfg->perm || cfg->n_perms >= 1, DDMI_ERR_ARG, "ddmi_pose_metrics_cfg: perm given with n_perms < 1");
+    Model& m = enter(h, cfg, "ddmi_pose_metrics_cfg");
+    check_pose_cfg(*cfg, "ddmi_pose_metrics_cfg");
     DDMI_REQUIRE(!cfg->points || cfg->n_points >= 1, DDMI_ERR_ARG, "ddmi_pose_metrics_cfg: points given with n_points < 1");
-    DDMI_CHECK_HIP(hipSetDevice(h->m.device));
-    pose_metrics(h->m, *cfg, (hipStream_t)s);
+    pose_metrics(m, *cfg, (hipStream_t)s);
   });
 }
 
 int ddmi_pose_fit(ddmi_model* h, const ddmi_pose_fit_cfg* cfg, ddmi_stream s) {
   return guard([&] {
-    DDMI_REQUIRE(h && cfg, DDMI_ERR_ARG, "null argument");
-    DDMI_REQUIRE(cfg->struct_size == sizeof(ddmi_pose_fit_cfg), DDMI_ERR_ARG, "ddmi_pose_fit_cfg.struct_size does not match this library");
-    DDMI_REQUIRE(cfg->pos && cfg->ref, DDMI_ERR_ARG, "ddmi_pose_fit_cfg: pos and ref are required");
-    DDMI_REQUIRE(cfg->n_poses > 0 && cfg->n_atoms > 0 && cfg->n_kept > 0 && cfg->n_refs > 0, DDMI_ERR_ARG,
-                 "ddmi_pose_fit_cfg: n_poses, n_atoms, n_kept and n_refs must be positive");
-    DDMI_REQUIRE(cfg->n_kept <= cfg->n_atoms, DDMI_ERR_ARG, "ddmi_pose_fit_cfg: n_kept > n_atoms");
-    DDMI_REQUIRE(cfg->atom_index || cfg->n_kept == cfg->n_atoms, DDMI_ERR_ARG, "ddmi_pose_fit_cfg: without atom_index n_kept must equal n_atoms");
-    DDMI_REQUIRE(!cfg->perm || cfg->n_perms >= 1, DDMI_ERR_ARG, "ddmi_pose_fit_cfg: perm given with n_perms < 1");
-    DDMI_CHECK_HIP(hipSetDevice(h->m.device));
-    pose_fit(h->m, *cfg, (hipStream_t)s);
+    Model& m = enter(h, cfg, "ddmi_pose_fit_cfg");
+    check_pose_cfg(*cfg, "ddmi_pose_fit_cfg");
+    pose_fit(m, *cfg, (hipStream_t)s);
   });
 }
 
 int ddmi_neighbor_graph(ddmi_model* h, const ddmi_neighbor_graph_cfg* cfg, ddmi_stream s) {
   return guard([&] {
-    DDMI_REQUIRE(h && cfg, DDMI_ERR_ARG, "null argument");
-    DDMI_REQUIRE(cfg->struct_size == sizeof(ddmi_neighbor_graph_cfg), DDMI_ERR_ARG, "ddmi_neighbor_graph_cfg.struct_size does not match this library");
+    Model& m = enter(h, cfg, "ddmi_neighbor_graph_cfg");
     DDMI_REQUIRE(cfg->pos && cfg->ptr, DDMI_ERR_ARG, "ddmi_neighbor_graph_cfg: pos and ptr are required");
     DDMI_REQUIRE(cfg->n_nodes > 0 && cfg->n_sets > 0, DDMI_ERR_ARG, "ddmi_neighbor_graph_cfg: n_nodes and n_sets must be positive");
-    DDMI_CHECK_HIP(hipSetDevice(h->m.device));
-    neighbor_graph(h->m, *cfg, (hipStream_t)s);
+    neighbor_graph(m, *cfg, (hipStream_t)s);
   });
 }
 
 int ddmi_match_conformer(ddmi_model* h, const ddmi_match_cfg* cfg, ddmi_stream s) {
   return guard([&] {
-    DDMI_REQUIRE(h && cfg, DDMI_ERR_ARG, "null argument");
-    DDMI_REQUIRE(cfg->struct_size == sizeof(ddmi_match_cfg), DDMI_ERR_ARG, "ddmi_match_cfg.struct_size does not match this library");
+    Model& m = enter(h, cfg, "ddmi_match_cfg");
     DDMI_REQUIRE(cfg->start && cfg->target && cfg->lig_ptr && cfg->tor_ptr, DDMI_ERR_ARG,
                  "ddmi_match_cfg: start, target, lig_ptr and tor_ptr are required");
     DDMI_REQUIRE(cfg->n_jobs >= 1, DDMI_ERR_ARG, "ddmi_match_cfg: n_jobs must be positive");
@@ -284,8 +278,7 @@ int ddmi_match_conformer(ddmi_model* h, const ddmi_match_cfg* cfg, ddmi_stream s
     DDMI_REQUIRE(cfg->tol >= 0.f, DDMI_ERR_ARG, "ddmi_match_cfg: tol must not be negative");   // (false for NaN)
     DDMI_REQUIRE(cfg->n_init >= 0 && (cfg->n_init == 0 || cfg->init_angles || cfg->tor_ptr[cfg->n_jobs] == 0), DDMI_ERR_ARG,
                  "ddmi_match_cfg: n_init must not be negative, and n_init > 0 needs init_angles");
-    DDMI_CHECK_HIP(hipSetDevice(h->m.device));
-    match_conformer(h->m, *cfg, (hipStream_t)s);
+    match_conformer(m, *cfg, (hipStream_t)s);
   });
 }
 
@@ -298,9 +291,8 @@ int ddmi_set_sample_record(ddmi_model* h, const ddmi_sample_record* r) {
 
 int ddmi_perturb(ddmi_model* h, float* tr, float* rot, float* tor, const ddmi_sample_cfg* cfg, int step, ddmi_stream s) {
   return guard([&] {
-    DDMI_REQUIRE(h && tr && rot && cfg, DDMI_ERR_ARG, "null argument");
-    DDMI_CHECK_HIP(hipSetDevice(h->m.device));
-    perturb(h->m, tr, rot, tor, *cfg, step, (hipStream_t)s);
+    Model& m = enter(h, tr && rot && cfg);
+    perturb(m, tr, rot, tor, *cfg, step, (hipStream_t)s);
   });
 }
 

@@ -1,4 +1,4 @@
-// Private to the host orchestration (complex.cpp, conv_layers.cpp, forward.cpp, sample.cpp): the per-complex state Model::Cx, the
+// Private to the host orchestration (complex.cpp, conv_layers.cpp, forward.cpp, sample.cpp; not standalone.cpp): the per-complex state Model::Cx, the
 // description of an edge group and the few helpers all four share.  Not installed, not included by kernels.
 #pragma once
 #include <algorithm>
@@ -98,16 +98,9 @@ struct Model::Cx {
   int* c_xrow;
   int *t_cnt, *t_atom; float *t_dist, *t_nvec, *t_ew, *t_bond_nvec, *t_ea, *t_attr, *t_hid, *t_W, *t_sh, *t_out, *t_feat;
   // sampler
-  float *s_tr, *s_rot, *s_tor, *s_t = nullptr; long long* s_ids = nullptr;
-  long long* s_ids_host = nullptr; hipEvent_t s_ids_ev = nullptr;   // pinned staging of the sample ids
+  float *s_tr, *s_rot, *s_tor, *s_t = nullptr; long long* s_ids = nullptr; PinnedStage s_ids_stage;   // s_ids [B] and its pinned staging
   bool rec_on = false; ddmi_sample_record rec{};   // ddmi_set_sample_record: caller-owned per-step arrays of the ddmi_sample loop
-  float *rp_center = nullptr, *rp_center_host = nullptr; hipEvent_t rp_ev = nullptr;   // ddmi_randomize_position: centres [B][3] and their pinned staging
-  ~Cx() {
-    if (s_ids_host) (void)hipHostFree(s_ids_host);
-    if (s_ids_ev) (void)hipEventDestroy(s_ids_ev);
-    if (rp_center_host) (void)hipHostFree(rp_center_host);
-    if (rp_ev) (void)hipEventDestroy(rp_ev);
-  }
+  float* rp_center = nullptr; PinnedStage rp_stage;   // ddmi_randomize_position: centres [B][3] and their pinned staging
 };
 
 typedef Model::Cx Cx;

@@ -18,8 +18,9 @@ struct HostTensor {
   int64_t numel() const { int64_t n = 1; for (auto d : shape) n *= d; return n; }
 };
 
+struct NoCopy { NoCopy() = default; NoCopy(const NoCopy&) = delete; NoCopy& operator=(const NoCopy&) = delete; };
 // Bump allocator over one hipMalloc'ed slab (freed with the owner).
-class DevicePool {
+class DevicePool : NoCopy {
  public:
   ~DevicePool();
   void* alloc_bytes(size_t n);
@@ -34,6 +35,20 @@ class DevicePool {
  private:
   std::vector<void*> blocks_;
   size_t total_ = 0;
+};
+// A pinned host buffer and the event guarding its reuse: a caller's array rides through it, consumed before the call returns; nothing waits for the stream.
+class PinnedStage : NoCopy {
+  void* buf_ = nullptr; size_t cap_ = 0; hipEvent_t ev_ = nullptr;
+ public:
+  ~PinnedStage();                                    // waits for the upload in flight
+  void* host(size_t n);                              // >= n bytes (grows, never shrinks), once the previous upload has left them
+  void upload(void* dst, size_t n, hipStream_t s);   // the first n bytes to a device address; records the event
+};
+// One device block that grows and never shrinks (hipFree waits for the device, so kernels of an earlier call still in flight keep their memory).
+class GrowScratch {
+  DevicePool pool_; char* block_ = nullptr; size_t bytes_ = 0;
+ public:
+  char* reserve(size_t bytes);   // the block when it is large enough, otherwise a new one
 };
 
 struct ConvW {  // one TensorProductConvLayer
@@ -138,11 +153,7 @@ struct Model {
   bool uniform_t = false;   // the forward in flight has one t for every graph of the batch (set by the device step loop, sample())
   double crop_cutoff = 0.0;  // > 0: receptor cropped to this distance from the ligand in ddmi_forward (crop_beyond)
   DevicePool cpool;
-  DevicePool mpool; void* metrics_ws = nullptr; size_t metrics_ws_bytes = 0;   // ddmi_pose_metrics / ddmi_pose_fit scratch: grows, never shrinks
-  DevicePool npool; void* nbr_ws = nullptr; size_t nbr_ws_bytes = 0;           // ddmi_neighbor_graph scratch: grows, never shrinks
-  int32_t* nbr_host = nullptr; size_t nbr_host_words = 0; hipEvent_t nbr_ev = nullptr;   // pinned staging of its per-set table
-  DevicePool xpool; void* match_ws = nullptr; size_t match_ws_bytes = 0;       // ddmi_match_conformer scratch: grows, never shrinks
-  char* match_host = nullptr; size_t match_host_bytes = 0; hipEvent_t match_ev = nullptr;   // pinned staging of its per-job tables
+  GrowScratch metrics_ws, nbr_ws, match_ws; PinnedStage nbr_stage, match_stage;   // standalone.cpp: scratch (pose metrics and fit share one) and table stagings
   struct Cx;  // cx.h
   std::shared_ptr<Cx> cx;
   std::map<std::string, DebugEntry> debug;
@@ -175,22 +186,18 @@ void set_batch_layout(Model& m, const ddmi_batch_layout& l, hipStream_t s);
 void forward(Model& m, const float* lig_pos, const float* t_tr, const float* t_rot, const float* t_tor, float* tr_out,
              float* rot_out, float* tor_out, hipStream_t s, float* conf_out = nullptr, float* atom_conf_out = nullptr);
 void sidechain_pred(Model& m, float* out, hipStream_t s);   // model(batch)[3] of the last forward (models/cg_model.py:397-402)
-// sample.cpp
-// rec_pos: nullptr, or a row of ddmi_sample_record.pos that receives the updated coordinates as well
-void modify_conformer(Model& m, float* lig_pos, const float* tr, const float* rot, const float* tor, hipStream_t s,
-                      float* rec_pos = nullptr);
+// sample.cpp (rec_pos: nullptr, or a row of ddmi_sample_record.pos that receives the updated coordinates as well)
+void modify_conformer(Model& m, float* lig_pos, const float* tr, const float* rot, const float* tor, hipStream_t s, float* rec_pos = nullptr);
 void set_sample_record(Model& m, const ddmi_sample_record* r);   // nullptr = off
 void sample(Model& m, float* lig_pos, const ddmi_sample_cfg& sc, hipStream_t s);
 // NaN guard + score / noise combination of step k (utils/sampling.py:117-186) on score arrays, in place
 void perturb(Model& m, float* tr, float* rot, float* tor, const ddmi_sample_cfg& sc, int k, hipStream_t s);
 // initial poses (utils/sampling.py:16-58) of every graph of the batch, in place
 void randomize_position(Model& m, float* lig_pos, const ddmi_randomize_cfg& rc, hipStream_t s);
-// RMSDs and clearances of poses against reference poses (evaluate.py:474-505); needs no complex
-void pose_metrics(Model& m, const ddmi_pose_metrics_cfg& mc, hipStream_t s);
+// standalone.cpp: the calls that need no complex
+void pose_metrics(Model& m, const ddmi_pose_metrics_cfg& mc, hipStream_t s);   // RMSDs and clearances of poses against reference poses (evaluate.py:474-505)
 void pose_fit(Model& m, const ddmi_pose_fit_cfg& fc, hipStream_t s);
-// capped neighbour lists of a ragged batch of point sets (process_mols.py:171-192, :207-228); needs no complex
-void neighbor_graph(Model& m, const ddmi_neighbor_graph_cfg& nc, hipStream_t s);
-// conformer matching of a ragged batch of jobs (datasets/conformer_matching.py); needs no complex
-void match_conformer(Model& m, const ddmi_match_cfg& mc, hipStream_t s);
+void neighbor_graph(Model& m, const ddmi_neighbor_graph_cfg& nc, hipStream_t s);   // capped neighbour lists of point sets (process_mols.py:171-192, :207-228)
+void match_conformer(Model& m, const ddmi_match_cfg& mc, hipStream_t s);           // conformer matching of a ragged batch of jobs (conformer_matching.py)
 
 }  // namespace ddmi

@@ -26,6 +26,34 @@ void* DevicePool::alloc_bytes(size_t n) {
   return p;
 }
 
+PinnedStage::~PinnedStage() {
+  if (ev_) { (void)hipEventSynchronize(ev_); (void)hipEventDestroy(ev_); }
+  if (buf_) (void)hipHostFree(buf_);
+}
+void* PinnedStage::host(size_t n) {
+  if (ev_) DDMI_CHECK_HIP(hipEventSynchronize(ev_));
+  else DDMI_CHECK_HIP(hipEventCreate(&ev_));
+  if (n > cap_) {   // the capacity is dropped first: a failed allocation leaves an empty stage
+    if (buf_) { (void)hipHostFree(buf_); buf_ = nullptr; cap_ = 0; }
+    DDMI_CHECK_HIP(hipHostMalloc(&buf_, n));
+    cap_ = n;
+  }
+  return buf_;
+}
+void PinnedStage::upload(void* dst, size_t n, hipStream_t s) {
+  DDMI_CHECK_HIP(hipMemcpyAsync(dst, buf_, n, hipMemcpyHostToDevice, s));
+  DDMI_CHECK_HIP(hipEventRecord(ev_, s));
+}
+
+char* GrowScratch::reserve(size_t bytes) {
+  if (bytes <= bytes_) return block_;
+  pool_.release();
+  block_ = nullptr; bytes_ = 0;   // (a failed allocation leaves an empty scratch)
+  block_ = static_cast<char*>(pool_.alloc_bytes(bytes));
+  bytes_ = bytes;
+  return block_;
+}
+
 static Irreps layer_irreps(const ddmi_config& c, int i) {
   const int ns = c.ns, nv = c.nv, last = c.reduce_pseudoscalars ? nv : ns;
   i = std::min(i, 3);

@@ -157,6 +157,22 @@ class MIScoreModel:
             return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         return None
 
+    def _keep_alive(self, tensors):
+        """Tensors that enqueued work reads must outlive it: on a CUDA device they are recorded on the current stream."""
+        if self.device.type == "cuda":
+            for t in tensors:
+                if t is not None:
+                    t.record_stream(torch.cuda.current_stream(self.device))
+
+    def _call_cfg(self, fn, cfg, inputs, outputs, empty_is_null=False):
+        """fn(handle, cfg, stream) with the pointer fields of `cfg` set from the tensors of the two dicts by field name (None, and with
+        `empty_is_null` an empty tensor, = NULL); the converted copies in `inputs` are kept alive.  Returns `outputs`."""
+        for name, t in list(inputs.items()) + list(outputs.items()):
+            setattr(cfg, name, None if t is None or (empty_is_null and t.numel() == 0) else t.data_ptr())
+        _lib.check(self.lib, fn(self._h, C.byref(cfg), self._stream()))
+        self._keep_alive(inputs.values())
+        return outputs
+
     def _static_tensors(self, data):
         lig, rec = data["ligand"], data["receptor"]
         bond, rr = data["ligand", "ligand"], data["receptor", "receptor"]
@@ -379,9 +395,7 @@ class MIScoreModel:
                 rc.tr_updates = dev_f32(draws["tr"], 3 * B)
         pos = data["ligand"].pos.to(dev, torch.float32).contiguous().clone()
         _lib.check(self.lib, self.lib.ddmi_randomize_position(self._h, _ptr(pos), C.byref(rc), self._stream()))
-        if dev.type == "cuda":   # the injected draws must outlive the enqueued kernel
-            for t in injected:
-                t.record_stream(torch.cuda.current_stream(dev))
+        self._keep_alive(injected)   # the injected draws must outlive the enqueued kernel
         return pos
 
     def _pose_inputs(self, pos, ref, perm, atom_index):
@@ -420,15 +434,7 @@ class MIScoreModel:
         fc.struct_size = C.sizeof(_lib.PoseFitCfg)
         fc.n_poses, fc.n_atoms, fc.n_kept, fc.n_refs = P, n, m, K
         fc.n_perms = 0 if perm is None else perm.shape[0]
-        inputs = dict(pos=pos, ref=ref, perm=perm, atom_index=atom_index)
-        for name, t in list(inputs.items()) + list(out.items()):
-            setattr(fc, name, None if t is None else t.data_ptr())
-        _lib.check(self.lib, self.lib.ddmi_pose_fit(self._h, C.byref(fc), self._stream()))
-        if dev.type == "cuda":   # converted copies of the inputs must outlive the enqueued kernels
-            for t in inputs.values():
-                if t is not None:
-                    t.record_stream(torch.cuda.current_stream(dev))
-        return out
+        return self._call_cfg(self.lib.ddmi_pose_fit, fc, dict(pos=pos, ref=ref, perm=perm, atom_index=atom_index), out)
 
     def match_conformer(self, start, target, lig_ptr, tor_ptr=None, rot_u=None, rot_v=None, mask_rotate=None, popsize=15, maxiter=500,
                         tol=0.01, seed=0, job_ids=None, init_angles=None, n_init=0):
@@ -482,14 +488,7 @@ class MIScoreModel:
         mc.lig_ptr, mc.tor_ptr = lig.ctypes.data, tor.ctypes.data
         mc.job_ids = None if ids is None else ids.ctypes.data
         inputs = dict(start=start, target=target, rot_u=rot_u, rot_v=rot_v, mask_rotate=mask_rotate, init_angles=init_angles)
-        for name, t in list(inputs.items()) + list(out.items()):
-            setattr(mc, name, None if t is None or t.numel() == 0 else t.data_ptr())
-        _lib.check(self.lib, self.lib.ddmi_match_conformer(self._h, C.byref(mc), self._stream()))
-        if dev.type == "cuda":   # converted copies of the inputs must outlive the enqueued kernels
-            for t in inputs.values():
-                if t is not None:
-                    t.record_stream(torch.cuda.current_stream(dev))
-        return out
+        return self._call_cfg(self.lib.ddmi_match_conformer, mc, inputs, out, empty_is_null=True)
 
     def pose_metrics(self, pos, ref, perm=None, atom_index=None, points=None, per_ref=False):
         """Judge poses on the device (ddmi_pose_metrics; evaluate.py:474-505): `pos` [P, n, 3] or a trajectory [T, P, n, 3], `ref`
@@ -516,14 +515,7 @@ class MIScoreModel:
         mc.n_perms = 0 if perm is None else perm.shape[0]
         mc.n_points = 0 if points is None else points.shape[0]
         inputs = dict(pos=pos, ref=ref, perm=perm, atom_index=atom_index, points=points)
-        for name, t in list(inputs.items()) + list(out.items()):
-            setattr(mc, name, None if t is None else t.data_ptr())
-        _lib.check(self.lib, self.lib.ddmi_pose_metrics(self._h, C.byref(mc), self._stream()))
-        if dev.type == "cuda":   # converted copies of the inputs must outlive the enqueued kernels
-            for t in inputs.values():
-                if t is not None:
-                    t.record_stream(torch.cuda.current_stream(dev))
-        return out
+        return self._call_cfg(self.lib.ddmi_pose_metrics, mc, inputs, out)
 
     def neighbor_graph(self, pos, cutoff, max_neighbors=None, ptr=None):
         """Capped neighbour lists on the device (ddmi_neighbor_graph; the loop of new_extract_receptor_structure,
@@ -572,8 +564,7 @@ class MIScoreModel:
             edge = torch.empty(2, E, dtype=torch.int64, device=dev)
             if E:
                 call(edge)
-        if dev.type == "cuda":
-            pos.record_stream(torch.cuda.current_stream(dev))
+        self._keep_alive([pos])
         return edge, deg
 
     def _sample_cfg(self, inference_steps, schedules, noise, seed, sample_ids, ode, no_random, no_final_step_noise,
@@ -628,10 +619,7 @@ class MIScoreModel:
         finally:
             if rec is not None:
                 _lib.set_sample_record(self.lib, self._h, off=True)
-        if noise is not None and self.device.type == "cuda":   # the injected draws must outlive the enqueued steps
-            for z in keep[2]:
-                if z is not None:
-                    z.record_stream(torch.cuda.current_stream(self.device))
+        self._keep_alive(keep[2])   # the injected draws must outlive the enqueued steps
         return pos if rec is None else (pos, rec)
 
     def _new_record(self, steps, parts):
@@ -663,10 +651,7 @@ class MIScoreModel:
         sc, keep = self._sample_cfg(inference_steps, schedules, noise, seed, sample_ids, ode, no_random, no_final_step_noise,
                                     temp_sampling, temp_psi, temp_sigma_data, None)
         _lib.check(self.lib, self.lib.ddmi_perturb(self._h, _ptr(tr), _ptr(rot), _ptr(tor), C.byref(sc), int(t_idx), self._stream()))
-        if noise is not None and self.device.type == "cuda":
-            for z in keep[2]:
-                if z is not None:
-                    z.record_stream(torch.cuda.current_stream(self.device))
+        self._keep_alive(keep[2])
         return tr, rot, tor
 
     # ------------------------------------------------------------------ introspection
